@@ -43,9 +43,24 @@ def main() -> None:
     p.add_argument("--prompt-pad", type=int, default=256,
                    help="synthetic observe-context words added to each prompt")
     p.add_argument("--model-config", choices=["30b", "tiny"], default="30b")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step "
+                        "returned to its callers as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary measurement or check; a "
+                        "plain run times the headline figure only (the "
+                        "benchmark has no secondary measurements today)")
     args = p.parse_args()
 
+    import random
+
     import torch
+
+    # fixed seeds: with the same arguments the weights, prompts and sampler
+    # seeds are identical from run to run; with the greedy decode below the
+    # replies are too, so --dump-outputs of two builds can be compared
+    random.seed(0)
+    torch.manual_seed(0)
 
     if args.model_config == "tiny":
         os.environ["ROOMAMD_MODEL_CONFIG"] = "tiny"
@@ -74,6 +89,7 @@ def main() -> None:
         engine = LocalEngine()
         set_local_engine(engine)
         register_engine(model_tag, engine)
+        _decode_greedily(engine)
         print(f"[rank {ctx.rank}] engine up: "
               f"{engine.model.num_params()/1e9:.1f}B params, "
               f"load {engine.load_seconds:.1f}s, "
@@ -107,11 +123,14 @@ def main() -> None:
     mgr = AgentLoopManager(ldb, memory=memsvc)
     pad = " ".join(f"obs{i} filler" for i in range(args.prompt_pad // 2))
 
+    last_results: list = []   # the latest step's per-agent execution results
+
     async def one_step() -> list[float]:
-        durations = await asyncio.gather(*[
+        cycles = await asyncio.gather(*[
             _cycle(mgr, room_id, wid, pad, args.decode_tokens)
             for wid in agent_ids])
-        return durations
+        last_results[:] = [res for _, res in cycles]
+        return [dur for dur, _ in cycles]
 
     from room_amd.core import quorum
     from room_amd.parallel.sync import SwarmSync
@@ -170,6 +189,9 @@ def main() -> None:
     ctx.barrier()
     elapsed = time.time() - t0
 
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, last_results, ctx.rank)
+
     # MAX over ranks
     el_t = torch.tensor([elapsed], dtype=torch.float64,
                         device=ctx.device if (use_gpu and ctx.is_distributed) else "cpu")
@@ -222,9 +244,57 @@ def main() -> None:
         print(json.dumps(out))
 
 
+def _decode_greedily(engine) -> None:
+    """Make the replies a function of the inputs: decode at temperature 0.
+
+    The expert-combine and split-K kernels accumulate with float atomics, so
+    logits differ in their last bits from run to run. At the agents' default
+    temperature 0.7 a draw that lands next to a bucket edge then picks
+    another token, and the reply, which is also the next step's prompt,
+    diverges for good (measured: two runs of one build agreed on a quarter
+    of the tokens). The arg-max is stable under that noise, so the benchmark
+    overrides the temperature alone; prompts, top-k/top-p, token counts, the
+    sampler kernel's top-k scan and the decode graphs are what the agents
+    use anyway."""
+    direct = engine.generate
+
+    def generate(*args, **kwargs):
+        kwargs["temperature"] = 0.0
+        return direct(*args, **kwargs)
+
+    engine.generate = generate
+
+
+def _dump_outputs(out_dir: str, results: list, rank: int) -> None:
+    """Write what the last timed step handed back to each agent's caller.
+
+    tokens.npy        float32 [agents, T]: token ids of each agent's reply
+                      text (the tokenizer round-trips generated ids exactly),
+                      rows padded with -1 to the longest reply
+    token_counts.npy  float32 [agents, 2]: (input_tokens, output_tokens)
+                      accounted to each agent's cycle
+    Ranks above 0 add a `_rank<r>` suffix to the names. A few KB in all.
+    """
+    import numpy as np
+
+    from room_amd.engine import tokenizer as tok
+
+    ids = [tok.encode(res.text or "") for res in results]
+    width = max((len(r) for r in ids), default=0)
+    tokens = np.full((len(ids), width), -1.0, dtype=np.float32)
+    for i, r in enumerate(ids):
+        tokens[i, :len(r)] = r
+    counts = np.array([[res.input_tokens, res.output_tokens] for res in results],
+                      dtype=np.float32).reshape(len(results), 2)
+    suffix = f"_rank{rank}" if rank else ""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"tokens{suffix}.npy"), tokens)
+    np.save(os.path.join(out_dir, f"token_counts{suffix}.npy"), counts)
+
+
 async def _cycle(mgr, room_id: int, worker_id: int, pad: str,
-                 decode_tokens: int) -> float:
-    """One agent cycle; returns wall seconds."""
+                 decode_tokens: int) -> tuple:
+    """One agent cycle; returns (wall seconds, execution result)."""
     from room_amd.db import queries as q
 
     t0 = time.time()
@@ -238,7 +308,7 @@ async def _cycle(mgr, room_id: int, worker_id: int, pad: str,
     res = out["result"]
     if not res.success:
         raise RuntimeError(f"cycle failed: {res.error}")
-    return time.time() - t0
+    return time.time() - t0, res
 
 
 if __name__ == "__main__":

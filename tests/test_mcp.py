@@ -1,6 +1,8 @@
 """MCP stdio server tests: JSON-RPC protocol + tool round-trips against the
 shared SQLite file (reference: src/mcp tests pattern)."""
 import json
+import os
+import tempfile
 
 import pytest
 
@@ -168,8 +170,10 @@ def test_parity_surface_tools(mcp):
     inv = call(mcp, "room_invite_create", {"room_id": rid})
     assert "error" in inv
 
-    # watch pause/resume
-    w = call(mcp, "room_watch_path", {"room_id": rid, "path": "/tmp/x",
+    # watch pause/resume (the allowlist admits home and the temp directory,
+    # wherever TMPDIR puts it)
+    watched = os.path.join(tempfile.gettempdir(), "x")
+    w = call(mcp, "room_watch_path", {"room_id": rid, "path": watched,
                                       "action_prompt": "check"})
     call(mcp, "room_pause_watch", {"watch_id": w["watch_id"]})
     call(mcp, "room_resume_watch", {"watch_id": w["watch_id"]})

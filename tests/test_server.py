@@ -132,13 +132,18 @@ def test_tasks_and_runs(server):
                     json={"name": "daily", "prompt": "do the thing",
                           "cron_expression": "0 9 * * *", "room_id": rid},
                     headers=h).json()
-    assert client.post(f"/api/tasks/{t['id']}/run", headers=h).json()["queued"]
     import time
-    for _ in range(300):
-        runs = client.get(f"/api/tasks/{t['id']}/runs", headers=h).json()
-        if runs and runs[0]["status"] != "running":
-            break
-        time.sleep(0.05)
+    # one event loop for the whole exchange, as in a running server: outside
+    # the context manager every request gets a loop of its own, and the
+    # queued run is cancelled with it unless it happens to finish first
+    with client:
+        assert client.post(f"/api/tasks/{t['id']}/run",
+                           headers=h).json()["queued"]
+        for _ in range(300):
+            runs = client.get(f"/api/tasks/{t['id']}/runs", headers=h).json()
+            if runs and runs[0]["status"] != "running":
+                break
+            time.sleep(0.05)
     assert runs and runs[0]["status"] == "completed"
     logs = client.get(f"/api/runs/{runs[0]['id']}/logs", headers=h).json()
     assert isinstance(logs, list)

@@ -375,7 +375,7 @@ class AgentLoopManager:
         # top-5 room memory via hybrid search on the objective context
         query = f"{room.get('goal') or room['name']}"
         vec = self.embed_fn(query) if self.embed_fn else None
-        semantic = (self.memory.store.search(vec, k=20)
+        semantic = (self.memory.store.search(vec, k=20, room_id=room["id"])
                     if (self.memory is not None and vec is not None) else None)
         hits = q.hybrid_search(db, query, vec, limit=MEMORY_TOP_K,
                                room_id=room["id"], semantic_hits=semantic)

@@ -215,7 +215,7 @@ def execute_agent_tool(db: sqlite3.Connection, room_id: int, worker_id: int,
                 vec = memory.embed(f"{args['name']} {args['content']}")
                 q.upsert_embedding(db, ent["id"], vec,
                                    memory.embedder.text_hash(args["content"]))
-                memory.store.upsert(ent["id"], vec)
+                memory.store.upsert(ent["id"], vec, room_id=room_id)
                 return json.dumps({"entity_id": ent["id"]})
             ent = q.get_entity_by_name(db, args["name"], room_id)
             if ent is None:
@@ -232,7 +232,7 @@ def execute_agent_tool(db: sqlite3.Connection, room_id: int, worker_id: int,
         if name == "room_recall":
             if memory is not None:
                 qvec = memory.embed(args["query"])
-                semantic = memory.store.search(qvec, k=20)
+                semantic = memory.store.search(qvec, k=20, room_id=room_id)
                 hits = q.hybrid_search(db, args["query"], qvec,
                                        limit=args.get("limit", 5), room_id=room_id,
                                        semantic_hits=semantic)

@@ -630,6 +630,15 @@ def all_embeddings(db: sqlite3.Connection, room_id: int | None = None) -> list[d
         "SELECT id, entity_id, vector, dimensions FROM embeddings").fetchall()
 
 
+def all_embeddings_with_room(db: sqlite3.Connection) -> list[dict]:
+    """Every durable embedding with its entity's room_id (None = global) —
+    the boot-path load of the room-tagged GPU vector store."""
+    return db.execute(
+        "SELECT m.id, m.entity_id, m.vector, m.dimensions, e.room_id"
+        " FROM embeddings m JOIN entities e ON e.id = m.entity_id"
+        " ORDER BY m.id").fetchall()
+
+
 def semantic_search_host(db: sqlite3.Connection, query_vec: list[float], limit: int = 10,
                          room_id: int | None = None) -> list[tuple[int, float]]:
     """Host-side brute-force cosine over stored blobs — durable fallback path.

@@ -332,6 +332,27 @@ def vs_topk(mat: torch.Tensor, query: torch.Tensor, k: int,
     return out_v, out_i
 
 
+def vs_topk_scoped(mat: torch.Tensor, tags: torch.Tensor, queries: torch.Tensor,
+                   scopes: torch.Tensor, k: int, nblocks: int = 512
+                   ) -> tuple[torch.Tensor, torch.Tensor]:
+    """Room-scoped cosine top-k for a batch of 1..8 queries in one pass over
+    the [N, 384] bf16 matrix. tags [N] int32 holds each row's room id (0 =
+    global row); scopes [Q] int32 holds -1 (every row) or a room id s (rows
+    tagged s or 0). Returns (values [Q, k] f32 descending, row indices [Q, k]
+    int64); slots beyond the rows in scope hold -inf / -1."""
+    dev = mat.device
+    nq = queries.size(0)
+    # the merge kernel holds every block's list head in one wave: ≤ 512 blocks
+    nblocks = min(nblocks, 512, max(1, (mat.size(0) + 255) // 256))
+    cand_v = torch.empty(nq, nblocks, k, dtype=torch.float32, device=dev)
+    cand_i = torch.empty(nq, nblocks, k, dtype=torch.int32, device=dev)
+    out_v = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    out_i = torch.empty(nq, k, dtype=torch.int64, device=dev)
+    _require().vs_topk_scoped(out_v, out_i, cand_v, cand_i, mat, tags, queries,
+                              scopes, k)
+    return out_v, out_i
+
+
 def build_moe_tile_desc(pair_expert_sorted: torch.Tensor, n_tiles_n: int,
                         num_experts: int, bm: int = 16) -> torch.Tensor:
     """Tile descriptors for the grouped MFMA GEMM: one row

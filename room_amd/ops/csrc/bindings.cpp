@@ -89,6 +89,10 @@ void hist_append(torch::Tensor hist, torch::Tensor ctr, torch::Tensor toks,
 void vs_topk(torch::Tensor out_v, torch::Tensor out_i, torch::Tensor cand_v,
              torch::Tensor cand_i, torch::Tensor mat, torch::Tensor query,
              int64_t K);
+void vs_topk_scoped(torch::Tensor out_v, torch::Tensor out_i,
+                    torch::Tensor cand_v, torch::Tensor cand_i,
+                    torch::Tensor mat, torch::Tensor tags,
+                    torch::Tensor queries, torch::Tensor scopes, int64_t K);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm", &rmsnorm, "RMSNorm (bf16, CDNA4)");
@@ -132,4 +136,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_scan_probe", &sample_scan_probe, "scan-cost probe");
   m.def("hist_append", &hist_append, "token-history append (multi-step decode)");
   m.def("vs_topk", &vs_topk, "vector-store cosine top-k over bf16 matrix");
+  m.def("vs_topk_scoped", &vs_topk_scoped,
+        "room-scoped cosine top-k for a batch of up to 8 queries");
 }

@@ -109,3 +109,23 @@ def vs_topk_ref(mat: torch.Tensor, query: torch.Tensor, k: int
     scores = mat.float() @ query.float()
     v, i = scores.topk(k)
     return v, i
+
+
+def vs_topk_scoped_ref(mat: torch.Tensor, tags: torch.Tensor,
+                       queries: torch.Tensor, scopes: torch.Tensor, k: int
+                       ) -> tuple[torch.Tensor, torch.Tensor]:
+    """Scope rule: scope < 0 admits every row; scope s admits rows tagged s
+    or 0 (global). Slots beyond the rows in scope hold -inf / -1."""
+    scores = (mat.float() @ queries.float().T).T            # [Q, N]
+    sc = scopes.view(-1, 1)
+    tg = tags.view(1, -1)
+    admit = (sc < 0) | (tg == 0) | (tg == sc)                # [Q, N]
+    scores = scores.masked_fill(~admit, float("-inf"))
+    kk = min(k, scores.size(1))
+    v, i = scores.topk(kk, dim=1)
+    i = i.masked_fill(v == float("-inf"), -1)
+    if kk < k:
+        pad = (scores.size(0), k - kk)
+        v = torch.cat([v, v.new_full(pad, float("-inf"))], dim=1)
+        i = torch.cat([i, i.new_full(pad, -1)], dim=1)
+    return v, i

@@ -54,6 +54,25 @@ class Qwen3MoEConfig:
                               moe_intermediate_size=256, max_position=4096)
 
 
+@dataclass
+class _Step:
+    """Per-forward inputs and buffers shared by every layer of one forward()
+    call (nothing here outlives the call)."""
+    seq_ids: torch.Tensor
+    q_pos: torch.Tensor
+    block_table: torch.Tensor
+    qtile_desc: torch.Tensor | None
+    hbuf: torch.Tensor                      # normed activations [T, H]
+    pair_token: torch.Tensor | None = None  # MoE pair -> token row [T*K]
+    pair_row: torch.Tensor | None = None    # identity pair map [T*K]
+    # decode-only (T ≤ 8) buffers
+    qkv: torch.Tensor | None = None
+    empty_delta: torch.Tensor | None = None
+    part: torch.Tensor | None = None
+    part_ml: torch.Tensor | None = None
+    obuf: torch.Tensor | None = None
+
+
 class Qwen3MoELayer:
     def __init__(self, cfg: Qwen3MoEConfig, device: torch.device, gen: torch.Generator):
         h, d = cfg.hidden_size, cfg.head_dim
@@ -93,20 +112,6 @@ class Qwen3MoEModel:
         self.final_norm_w = torch.ones(h, dtype=torch.bfloat16, device=self.device)
         self.lm_head = torch.empty(cfg.vocab_size, h, dtype=torch.bfloat16,
                                    device=self.device).normal_(0, 0.02, generator=gen)
-        import os as _os
-        self._moe_scratch: dict = {}   # dedup-GEMV persistent buffers
-        self.moe_dedup = _os.environ.get('ROOMAMD_MOE_DEDUP') == '1'
-        # fused decode kernels (attn_merge_o / router_addnorm): measured
-        # SLOWER than the two-kernel paths at B=5 (profiles/PERF_NOTES.md
-        # round-2 negative results — attn_merge_o re-reads the split partials
-        # once per output tile, 16× redundant HBM traffic, 31.8 µs vs the
-        # 19.4 µs merge+GEMV pair; router_addnorm 10.9 vs 9.75 on a
-        # latency-starved 32-WG grid). Kept behind env for the record.
-        self.fuse_o = _os.environ.get('ROOMAMD_FUSE_O') == '1'
-        self.fuse_router = _os.environ.get('ROOMAMD_FUSE_ROUTER') == '1'
-        # grouped-GEMM m-tile: 256 halves expert-panel re-reads when experts
-        # average >=128 pairs (prefill chunks >=2k tokens)
-        self.moe_bm = 256 if _os.environ.get('ROOMAMD_MOE_BM') == '256' else 128
         # decode split-KV band (32 short / 64 long contexts); the engine sets
         # this per decode step (and per captured graph band)
         self.attn_splits = 32
@@ -136,7 +141,7 @@ class Qwen3MoEModel:
         dp = self._dense_desc.get(T)
         if dp is None:
             pe = torch.zeros(T, dtype=torch.int32, device=x.device)
-            desc = ops.moe_build_desc_device(pe, 1, bm=128)
+            desc = ops.moe_build_desc_device(pe, 1)
             pt = torch.arange(T, dtype=torch.int32, device=x.device)
             dp = self._dense_desc[T] = (desc, pt)
         N = w.size(0)
@@ -171,136 +176,44 @@ class Qwen3MoEModel:
         qdim = cfg.num_q_heads * cfg.head_dim
         kvdim = cfg.num_kv_heads * cfg.head_dim
         x = self.embed[tokens.long()]              # [T, H] bf16 (residual stream)
-        hbuf = torch.empty_like(x)                 # normed activations
+        # per-forward state shared by every layer
+        st = _Step(seq_ids=seq_ids, q_pos=q_pos, block_table=block_table,
+                   qtile_desc=qtile_desc,
+                   hbuf=torch.empty_like(x))       # normed activations
         moe_out = None                             # pending delta for fused add
         # layer-invariant MoE pair/token indices (was re-built 48×/step: an
         # arange+repeat_interleave kernel pair per layer in the decode graph)
         K = cfg.num_experts_per_tok
-        self._pair_token_flat = torch.arange(
+        st.pair_token = torch.arange(
             T, device=dev, dtype=torch.int32).repeat_interleave(K)
-        self._arangeP = torch.arange(T * K, device=dev, dtype=torch.int32)
+        st.pair_row = torch.arange(T * K, device=dev, dtype=torch.int32)
         if decode:
-            qkv = torch.empty(T, qdim + 2 * kvdim, dtype=torch.bfloat16, device=dev)
+            st.qkv = torch.empty(T, qdim + 2 * kvdim, dtype=torch.bfloat16,
+                                 device=dev)
             x_alt = torch.empty_like(x)     # residual ping-pong for fused norms
-            empty_delta = torch.empty(0, dtype=torch.float32, device=dev)
+            st.empty_delta = torch.empty(0, dtype=torch.float32, device=dev)
             nsp = ops.attn_nsplits()
-            part = torch.empty(T, cfg.num_q_heads, nsp, cfg.head_dim,
-                               dtype=torch.float32, device=dev)
-            part_ml = torch.empty(T, cfg.num_q_heads, nsp, 2, dtype=torch.float32,
+            st.part = torch.empty(T, cfg.num_q_heads, nsp, cfg.head_dim,
+                                  dtype=torch.float32, device=dev)
+            st.part_ml = torch.empty(T, cfg.num_q_heads, nsp, 2,
+                                     dtype=torch.float32, device=dev)
+            st.obuf = torch.empty(T, cfg.hidden_size, dtype=torch.bfloat16,
                                   device=dev)
-            # fused decode path (attn_merge_o / router_addnorm): collapses
-            # merge+O-GEMV and add-norm+router-partial into single kernels
-            fuse_o, fuse_router = self.fuse_o, self.fuse_router
-            if fuse_o:
-                o_accum = torch.empty(T, cfg.hidden_size, dtype=torch.float32,
-                                      device=dev)
-            else:
-                obuf = torch.empty(T, cfg.hidden_size, dtype=torch.bfloat16,
-                                   device=dev)
-            if fuse_router:
-                rlogits = torch.empty(T, cfg.num_experts, dtype=torch.float32,
-                                      device=dev)
 
         for li, layer in enumerate(self.layers):
-            # --- attention block
-            if decode and T <= 2:
-                # fused add(moe_prev)+RMSNorm+QKV-GEMV: one kernel replaces
-                # fused_add_rmsnorm + gemv. Wins at B≤2 where the removed
-                # launch/drain bubble dominates (5.7 → 5.2 ms/step at B=1);
-                # at B≥3 the cooperative norm passes cost more than the bubble
-                # (measured 9.1 vs 8.8 at B=5) so the unfused path is used.
-                if moe_out is None:
-                    ops.gemv_addnorm(qkv, x, empty_delta, x, layer.input_norm_w,
-                                     layer.wqkv, cfg.rms_eps)
-                else:
-                    ops.gemv_addnorm(qkv, x, moe_out, x_alt, layer.input_norm_w,
-                                     layer.wqkv, cfg.rms_eps)
-                    x, x_alt = x_alt, x
-            elif decode:
-                if moe_out is None:
-                    ops.rmsnorm(hbuf, x, layer.input_norm_w, cfg.rms_eps)
-                else:
-                    ops.fused_add_rmsnorm(hbuf, x, moe_out, layer.input_norm_w,
-                                          cfg.rms_eps)
-                ops.gemv(qkv, hbuf, layer.wqkv)
-            else:
-                if moe_out is None:
-                    ops.rmsnorm(hbuf, x, layer.input_norm_w, cfg.rms_eps)
-                else:
-                    ops.fused_add_rmsnorm(hbuf, x, moe_out, layer.input_norm_w,
-                                          cfg.rms_eps)
-                qkv = self._dense(hbuf, layer.wqkv)
-            # q stays a strided view into qkv (the attention kernels take a
-            # row stride; .contiguous() copies profiled at 0.67 ms/step)
-            q = qkv[:, :qdim].view(T, cfg.num_q_heads, cfg.head_dim)
-            ops.qk_rope_write_kv(qkv, cfg.num_q_heads, kcaches[li], vcaches[li],
-                                 layer.q_norm_w, layer.k_norm_w, self.cos_t,
-                                 self.sin_t, block_table, seq_ids, q_pos,
-                                 cfg.rms_eps)
             if decode:
-                if fuse_o:
-                    # split partials (+zero the O accumulator as a side job),
-                    # then one kernel merges per-head and projects through Wo
-                    # with f32 atomics — no bf16 attn round-trip
-                    ops.paged_attention_splitk(part, part_ml, q, kcaches[li],
-                                               vcaches[li], block_table,
-                                               seq_ids, q_pos, self.scale,
-                                               o_accum,
-                                               splits=self.attn_splits)
-                    ops.attn_merge_o(o_accum, part, part_ml, layer.wo,
-                                     splits=self.attn_splits)
-                    o = o_accum                   # f32 delta
-                else:
-                    attn = torch.empty(T, cfg.num_q_heads, cfg.head_dim,
-                                       dtype=torch.bfloat16, device=dev)
-                    ops.paged_attention_split(attn, q, kcaches[li],
-                                              vcaches[li], block_table,
-                                              seq_ids, q_pos, part, part_ml,
-                                              self.scale,
-                                              splits=self.attn_splits)
-                    ops.gemv(obuf, attn.reshape(T, qdim), layer.wo)
-                    o = obuf
-                # --- MoE block
-                if fuse_router:
-                    # add+norm+router logits in one kernel
-                    ops.router_addnorm(rlogits, x, o, x_alt, hbuf,
-                                       layer.post_attn_norm_w, layer.router_w,
-                                       cfg.rms_eps)
-                    x, x_alt = x_alt, x
-                    topk_ids, topk_w = ops.moe_router(rlogits,
-                                                      cfg.num_experts_per_tok)
-                else:
-                    ops.fused_add_rmsnorm(hbuf, x, o, layer.post_attn_norm_w,
-                                          cfg.rms_eps)
-                    topk_ids, topk_w = ops.router_gemv_topk(
-                        hbuf, layer.router_w, cfg.num_experts_per_tok)
-                moe_out = self._moe(hbuf, layer, topk_ids, topk_w)
-                continue
-            attn = torch.empty(T, cfg.num_q_heads, cfg.head_dim,
-                               dtype=torch.bfloat16, device=dev)
-            if qtile_desc is not None:
-                ops.flash_prefill(attn, q, kcaches[li], vcaches[li], block_table,
-                                  seq_ids, q_pos, qtile_desc, self.scale)
-                o = self._dense(attn.reshape(T, qdim), layer.wo)
+                x, x_alt, moe_out = self._decode_layer(
+                    layer, kcaches[li], vcaches[li], st, x, x_alt, moe_out)
             else:
-                ops.paged_attention(attn, q, kcaches[li], vcaches[li], block_table,
-                                    seq_ids, q_pos, self.scale)
-                o = F.linear(attn.reshape(T, qdim), layer.wo)
-
-            # --- MoE block (prefill; decode handled above)
-            ops.fused_add_rmsnorm(hbuf, x, o, layer.post_attn_norm_w, cfg.rms_eps)
-            router_logits = self._dense(hbuf, layer.router_w).float()
-            topk_ids, topk_w = ops.moe_router(router_logits,
-                                              cfg.num_experts_per_tok)
-            # f32 accumulator feeds fused_add_rmsnorm directly (templated
-            # input dtype — skips a cast kernel per layer)
-            moe_out = self._moe(hbuf, layer, topk_ids, topk_w)
+                moe_out = self._prefill_layer(
+                    layer, kcaches[li], vcaches[li], st, x, moe_out)
 
         # final residual add + norm; skip lm_head entirely for logits-free
         # prefill chunks (an empty logits_rows means "no sampling this chunk")
         if logits_rows is not None and logits_rows.numel() == 0:
             return torch.empty(0, cfg.vocab_size, dtype=torch.float32,
                                device=x.device)
+        hbuf = st.hbuf
         ops.fused_add_rmsnorm(hbuf, x, moe_out, self.final_norm_w, cfg.rms_eps)
         sel = hbuf if logits_rows is None else hbuf[logits_rows.long()]
         if sel.size(0) <= 8:
@@ -313,25 +226,109 @@ class Qwen3MoEModel:
             logits = F.linear(sel, self.lm_head).float()
         return logits
 
+    def _decode_layer(self, layer: Qwen3MoELayer, kcache: torch.Tensor,
+                      vcache: torch.Tensor, st: "_Step", x: torch.Tensor,
+                      x_alt: torch.Tensor, moe_out: torch.Tensor | None):
+        """One layer at T ≤ 8: every projection on the hand-written GEMVs,
+        split-KV attention, pair-GEMV MoE. Returns (x, x_alt, moe_out); the
+        residual ping-pongs between x and x_alt at T ≤ 2."""
+        cfg = self.cfg
+        T = x.size(0)
+        qdim = cfg.num_q_heads * cfg.head_dim
+        hbuf, qkv = st.hbuf, st.qkv
+        # --- attention block
+        if T <= 2:
+            # fused add(moe_prev)+RMSNorm+QKV-GEMV: one kernel replaces
+            # fused_add_rmsnorm + gemv. Wins at B≤2 where the removed
+            # launch/drain bubble dominates (5.7 → 5.2 ms/step at B=1);
+            # at B≥3 the cooperative norm passes cost more than the bubble
+            # (measured 9.1 vs 8.8 at B=5) so the unfused path is used.
+            if moe_out is None:
+                ops.gemv_addnorm(qkv, x, st.empty_delta, x, layer.input_norm_w,
+                                 layer.wqkv, cfg.rms_eps)
+            else:
+                ops.gemv_addnorm(qkv, x, moe_out, x_alt, layer.input_norm_w,
+                                 layer.wqkv, cfg.rms_eps)
+                x, x_alt = x_alt, x
+        else:
+            if moe_out is None:
+                ops.rmsnorm(hbuf, x, layer.input_norm_w, cfg.rms_eps)
+            else:
+                ops.fused_add_rmsnorm(hbuf, x, moe_out, layer.input_norm_w,
+                                      cfg.rms_eps)
+            ops.gemv(qkv, hbuf, layer.wqkv)
+        # q stays a strided view into qkv (the attention kernels take a
+        # row stride; .contiguous() copies profiled at 0.67 ms/step)
+        q = qkv[:, :qdim].view(T, cfg.num_q_heads, cfg.head_dim)
+        ops.qk_rope_write_kv(qkv, cfg.num_q_heads, kcache, vcache,
+                             layer.q_norm_w, layer.k_norm_w, self.cos_t,
+                             self.sin_t, st.block_table, st.seq_ids, st.q_pos,
+                             cfg.rms_eps)
+        attn = torch.empty(T, cfg.num_q_heads, cfg.head_dim,
+                           dtype=torch.bfloat16, device=x.device)
+        ops.paged_attention_split(attn, q, kcache, vcache, st.block_table,
+                                  st.seq_ids, st.q_pos, st.part, st.part_ml,
+                                  self.scale, splits=self.attn_splits)
+        ops.gemv(st.obuf, attn.reshape(T, qdim), layer.wo)
+        # --- MoE block
+        ops.fused_add_rmsnorm(hbuf, x, st.obuf, layer.post_attn_norm_w,
+                              cfg.rms_eps)
+        topk_ids, topk_w = ops.router_gemv_topk(hbuf, layer.router_w,
+                                                cfg.num_experts_per_tok)
+        return x, x_alt, self._moe(hbuf, layer, topk_ids, topk_w, st)
+
+    def _prefill_layer(self, layer: Qwen3MoELayer, kcache: torch.Tensor,
+                       vcache: torch.Tensor, st: "_Step", x: torch.Tensor,
+                       moe_out: torch.Tensor | None) -> torch.Tensor:
+        """One layer at T > 8: dense projections through _dense, MFMA flash
+        prefill (or the unified paged kernel without q-tile descriptors),
+        grouped-GEMM MoE. x is updated in place; returns moe_out."""
+        cfg = self.cfg
+        T = x.size(0)
+        qdim = cfg.num_q_heads * cfg.head_dim
+        hbuf = st.hbuf
+        # --- attention block
+        if moe_out is None:
+            ops.rmsnorm(hbuf, x, layer.input_norm_w, cfg.rms_eps)
+        else:
+            ops.fused_add_rmsnorm(hbuf, x, moe_out, layer.input_norm_w,
+                                  cfg.rms_eps)
+        qkv = self._dense(hbuf, layer.wqkv)
+        q = qkv[:, :qdim].view(T, cfg.num_q_heads, cfg.head_dim)
+        ops.qk_rope_write_kv(qkv, cfg.num_q_heads, kcache, vcache,
+                             layer.q_norm_w, layer.k_norm_w, self.cos_t,
+                             self.sin_t, st.block_table, st.seq_ids, st.q_pos,
+                             cfg.rms_eps)
+        attn = torch.empty(T, cfg.num_q_heads, cfg.head_dim,
+                           dtype=torch.bfloat16, device=x.device)
+        if st.qtile_desc is not None:
+            ops.flash_prefill(attn, q, kcache, vcache, st.block_table,
+                              st.seq_ids, st.q_pos, st.qtile_desc, self.scale)
+            o = self._dense(attn.reshape(T, qdim), layer.wo)
+        else:
+            ops.paged_attention(attn, q, kcache, vcache, st.block_table,
+                                st.seq_ids, st.q_pos, self.scale)
+            o = F.linear(attn.reshape(T, qdim), layer.wo)
+        # --- MoE block
+        ops.fused_add_rmsnorm(hbuf, x, o, layer.post_attn_norm_w, cfg.rms_eps)
+        router_logits = self._dense(hbuf, layer.router_w).float()
+        topk_ids, topk_w = ops.moe_router(router_logits,
+                                          cfg.num_experts_per_tok)
+        return self._moe(hbuf, layer, topk_ids, topk_w, st)
+
     def _moe(self, hbuf: torch.Tensor, layer: Qwen3MoELayer,
-             topk_ids: torch.Tensor, topk_w: torch.Tensor) -> torch.Tensor:
+             topk_ids: torch.Tensor, topk_w: torch.Tensor,
+             st: "_Step") -> torch.Tensor:
         cfg = self.cfg
         T = hbuf.size(0)
-        K = cfg.num_experts_per_tok
         H, I = cfg.hidden_size, cfg.moe_intermediate_size
 
         if T < cfg.moe_grouped_threshold:
+            # GEMV per (token, expert) pair; the f32 accumulator feeds
+            # fused_add_rmsnorm directly (templated input dtype — skips a
+            # cast kernel per layer)
             out = torch.empty(T, H, dtype=torch.float32, device=hbuf.device)
-            if self.moe_dedup:
-                out.zero_()
-                # expert-deduped GEMV (weight rows once per active expert);
-                # measured slower than the pair path at B<=8 on random routing
-                # -- kept behind ROOMAMD_MOE_DEDUP=1 pending a win
-                ops.moe_gemv_dedup(out, hbuf, layer.w13, layer.w2, topk_ids,
-                                   topk_w, self._moe_scratch)
-                return out
-            # decode path: GEMV per (token, expert) pair
-            pair_token = self._pair_token_flat
+            pair_token = st.pair_token
             pair_expert = topk_ids.flatten().contiguous()
             pair_w = topk_w.flatten().contiguous()
             P = pair_token.numel()
@@ -341,23 +338,23 @@ class Qwen3MoEModel:
             ops.moe_gemv_down(out, h, layer.w2, pair_w, pair_token, pair_expert)
             return out
 
-        # prefill path: sort pairs by expert, grouped MFMA GEMMs
+        # sort pairs by expert, grouped MFMA GEMMs
         flat_expert = topk_ids.flatten()
         order = torch.argsort(flat_expert)
         pair_expert = flat_expert[order].int().contiguous()
-        pair_token = self._pair_token_flat[order].contiguous()
+        pair_token = st.pair_token[order].contiguous()
         P = pair_token.numel()
         inv_order = torch.empty_like(order)
         inv_order[order] = torch.arange(P, device=hbuf.device)
         inv_order = inv_order.int().contiguous()
-        bm = self.moe_bm
-        desc = ops.moe_build_desc_device(pair_expert, cfg.num_experts, bm=bm)
+        desc = ops.moe_build_desc_device(pair_expert, cfg.num_experts)
         gateup = torch.empty(P, 2 * I, dtype=torch.bfloat16, device=hbuf.device)
-        ops.moe_grouped_gemm128(gateup, hbuf, layer.w13, pair_token, desc, bm=bm)
+        ops.moe_grouped_gemm128(gateup, hbuf, layer.w13, pair_token, desc)
         h = torch.empty(P, I, dtype=torch.bfloat16, device=hbuf.device)
         ops.silu_mul(h, gateup)
         z = torch.empty(P, H, dtype=torch.bfloat16, device=hbuf.device)
-        ops.moe_grouped_gemm128(z, h, layer.w2, self._arangeP, desc, bm=bm)
+        # the down GEMM reads h rows per sorted pair: identity pair map
+        ops.moe_grouped_gemm128(z, h, layer.w2, st.pair_row, desc)
         out_bf = torch.empty(T, H, dtype=torch.bfloat16, device=hbuf.device)
         ops.moe_combine_gather(out_bf, z, topk_w.contiguous(), inv_order)
         return out_bf

@@ -109,40 +109,6 @@ def gemv(y: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return y
 
 
-def paged_attention_splitk(part: torch.Tensor, part_ml: torch.Tensor,
-                           q: torch.Tensor, kcache: torch.Tensor,
-                           vcache: torch.Tensor, block_table: torch.Tensor,
-                           seq_ids: torch.Tensor, q_pos: torch.Tensor,
-                           scale: float, o_zero: torch.Tensor,
-                           splits: int = 32) -> None:
-    """Split-KV decode attention, partials only (no bf16 merge output); zeros
-    `o_zero` (the attn_merge_o f32 accumulator) as a side job."""
-    _require().paged_attention_splitk(part, part_ml, q, kcache, vcache,
-                                      block_table, seq_ids, q_pos, scale,
-                                      o_zero, splits)
-
-
-def attn_merge_o(o_accum: torch.Tensor, part: torch.Tensor,
-                 part_ml: torch.Tensor, wo: torch.Tensor,
-                 splits: int = 32) -> torch.Tensor:
-    """Fused split-partial merge + O-projection: o_accum[B, H] (f32,
-    pre-zeroed) += Wo @ merged-attention. Replaces the standalone merge
-    kernel + O GEMV on the decode path."""
-    _require().attn_merge_o(o_accum, part, part_ml, wo, splits)
-    return o_accum
-
-
-def router_addnorm(y: torch.Tensor, x: torch.Tensor, delta: torch.Tensor,
-                   x_out: torch.Tensor, xn_out: torch.Tensor,
-                   gamma: torch.Tensor, w: torch.Tensor,
-                   eps: float = 1e-6) -> torch.Tensor:
-    """x_out = x + delta (f32); xn_out = rmsnorm(x_out)·γ; y = xn @ w^T
-    (f32 router logits). One kernel replaces fused_add_rmsnorm + the H-split
-    router partial GEMV on the decode path. x_out must not alias x."""
-    _require().router_addnorm(y, x, delta, x_out, xn_out, gamma, w, eps)
-    return y
-
-
 def flash_prefill(out: torch.Tensor, q: torch.Tensor, kcache: torch.Tensor,
                   vcache: torch.Tensor, block_table: torch.Tensor,
                   seq_ids: torch.Tensor, q_pos: torch.Tensor,
@@ -200,16 +166,6 @@ def router_gemv_topk(x: torch.Tensor, wr: torch.Tensor,
     return ids, w
 
 
-def router_topk(x: torch.Tensor, wr: torch.Tensor,
-                k: int) -> tuple[torch.Tensor, torch.Tensor]:
-    """Fused decode router: logits = x @ wr.T → softmax → top-k → renorm."""
-    T = x.size(0)
-    ids = torch.empty(T, k, dtype=torch.int32, device=x.device)
-    w = torch.empty(T, k, dtype=torch.float32, device=x.device)
-    _require().router_topk(ids, w, x, wr, k)
-    return ids, w
-
-
 def moe_gemv_h(h: torch.Tensor, x: torch.Tensor, w13: torch.Tensor,
                pair_token: torch.Tensor, pair_expert: torch.Tensor,
                out_zero: torch.Tensor | None = None) -> torch.Tensor:
@@ -228,59 +184,21 @@ def moe_gemv_down(out: torch.Tensor, h: torch.Tensor, w2: torch.Tensor,
     return out
 
 
-def moe_grouped_gemm(out: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
-                     pair_token: torch.Tensor, tile_desc: torch.Tensor) -> torch.Tensor:
-    _require().moe_grouped_gemm(out, x, w, pair_token, tile_desc)
-    return out
-
-
 def moe_grouped_gemm128(out: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
-                        pair_token: torch.Tensor, tile_desc: torch.Tensor,
-                        bm: int = 128) -> torch.Tensor:
-    """Grouped MFMA GEMM: expert weight panels read once per BM-row m-tile
-    (bm must match the tile_desc's build bm; 256 halves W traffic when
-    experts average ≥128 pairs)."""
-    _require().moe_grouped_gemm128(out, x, w, pair_token, tile_desc, bm)
+                        pair_token: torch.Tensor, tile_desc: torch.Tensor
+                        ) -> torch.Tensor:
+    """Grouped MFMA GEMM: expert weight panels read once per 128-row m-tile
+    (tile_desc from moe_build_desc_device)."""
+    _require().moe_grouped_gemm128(out, x, w, pair_token, tile_desc)
     return out
 
 
-def moe_combine(out: torch.Tensor, z: torch.Tensor, pair_w: torch.Tensor,
-                pair_token: torch.Tensor) -> torch.Tensor:
-    _require().moe_combine(out, z, pair_w, pair_token)
-    return out
-
-
-def moe_gemv_dedup(out: torch.Tensor, x: torch.Tensor, w13: torch.Tensor,
-                   w2: torch.Tensor, topk_ids: torch.Tensor,
-                   topk_w: torch.Tensor, scratch: dict) -> torch.Tensor:
-    """Expert-deduped decode MoE: weight rows read once per active expert.
-    scratch holds persistent buffers keyed by (E, I): counts/tok_list/w_list/h."""
-    E = w13.size(0)
-    I = w2.size(2)
-    key = (E, I)
-    if key not in scratch:
-        dev = x.device
-        scratch[key] = {
-            "counts": torch.zeros(E, dtype=torch.int32, device=dev),
-            "tok_list": torch.zeros(E, 64, dtype=torch.int32, device=dev),
-            "w_list": torch.zeros(E, 64, dtype=torch.float32, device=dev),
-            "h": torch.zeros(E * 64, I, dtype=torch.bfloat16, device=dev),
-            "active": torch.full((512,), -1, dtype=torch.int32, device=dev),
-        }
-    sc = scratch[key]
-    _require().moe_gemv_dedup(out, x, w13, w2, topk_ids.contiguous(),
-                              topk_w.contiguous(), sc["counts"],
-                              sc["tok_list"], sc["w_list"], sc["h"],
-                              sc["active"])
-    return out
-
-
-def moe_build_desc_device(pair_expert_sorted: torch.Tensor, num_experts: int,
-                          bm: int = 128) -> torch.Tensor:
-    """Sync-free [GMAX,3] (expert,row0,msize) descriptors; GMAX computed from
-    the host-known pair count, empty tiles zero-sized."""
+def moe_build_desc_device(pair_expert_sorted: torch.Tensor,
+                          num_experts: int) -> torch.Tensor:
+    """Sync-free [GMAX,3] (expert,row0,msize) descriptors of 128-row m-tiles;
+    GMAX computed from the host-known pair count, empty tiles zero-sized."""
     P = pair_expert_sorted.numel()
-    gmax = num_experts + (P + bm - 1) // bm
+    gmax = num_experts + (P + 127) // 128
     # NOT torch.bincount: its nbins probe (.max().item()) host-syncs, which
     # aborts hipGraph capture — scatter_add_ is sync-free
     counts = torch.zeros(num_experts, dtype=torch.int64,
@@ -290,7 +208,7 @@ def moe_build_desc_device(pair_expert_sorted: torch.Tensor, num_experts: int,
                                    device=pair_expert_sorted.device))
     desc = torch.empty(gmax, 3, dtype=torch.int32,
                        device=pair_expert_sorted.device)
-    _require().moe_build_desc(desc, counts, bm)
+    _require().moe_build_desc(desc, counts)
     return desc
 
 
@@ -301,7 +219,7 @@ def dense_grouped_gemm(y: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
     MFMA kernel with a single expert. hipBLASLt is faster eager but its
     internal calls abort hipGraph capture; inside captured prefill forwards
     this path runs instead (desc/pair_token prebuilt per T by the model)."""
-    _require().moe_grouped_gemm128(y, x, w.unsqueeze(0), pair_token, desc, 128)
+    _require().moe_grouped_gemm128(y, x, w.unsqueeze(0), pair_token, desc)
     return y
 
 
@@ -314,8 +232,8 @@ def moe_combine_gather(out: torch.Tensor, z: torch.Tensor, topk_w: torch.Tensor,
 def sample_tokens(logits: torch.Tensor, seeds: torch.Tensor, top_k: int = 40,
                   temperature: float = 0.7, top_p: float = 0.95) -> torch.Tensor:
     out = torch.empty(logits.size(0), dtype=torch.int32, device=logits.device)
-    # v3: register-resident top-8 scan + tournament (4× the v2 LDS variant)
-    _require().sample_tokens_v4(out, logits, seeds, top_k, temperature, top_p)
+    # two-stage sampler: per-slice register top-8 scan, then one wave per row
+    _require().sample_tokens(out, logits, seeds, top_k, temperature, top_p)
     return out
 
 
@@ -351,30 +269,3 @@ def vs_topk_scoped(mat: torch.Tensor, tags: torch.Tensor, queries: torch.Tensor,
     _require().vs_topk_scoped(out_v, out_i, cand_v, cand_i, mat, tags, queries,
                               scopes, k)
     return out_v, out_i
-
-
-def build_moe_tile_desc(pair_expert_sorted: torch.Tensor, n_tiles_n: int,
-                        num_experts: int, bm: int = 16) -> torch.Tensor:
-    """Tile descriptors for the grouped MFMA GEMM: one row
-    (expert, row_start, m_size, n_tile) per (M-tile × N-tile). Fully
-    vectorized on the device — no host sync (runs once per layer per step)."""
-    dev = pair_expert_sorted.device
-    counts = torch.zeros(num_experts, dtype=torch.int64, device=dev)
-    counts.scatter_add_(0, pair_expert_sorted.long(),
-                        torch.ones(pair_expert_sorted.numel(),
-                                   dtype=torch.int64, device=dev))
-    mtiles = (counts + bm - 1) // bm                      # [E]
-    e_ids = torch.repeat_interleave(
-        torch.arange(num_experts, device=dev), mtiles)    # [G_m]
-    starts = torch.cumsum(counts, 0) - counts             # row offset per expert
-    mt_off = torch.cumsum(mtiles, 0) - mtiles             # first tile idx per expert
-    g = e_ids.numel()
-    tile_in_e = torch.arange(g, device=dev) - mt_off[e_ids]
-    row_start = starts[e_ids] + bm * tile_in_e
-    m_size = torch.minimum(counts[e_ids] - bm * tile_in_e,
-                           torch.full_like(row_start, bm))
-    desc_m = torch.stack([e_ids, row_start, m_size], dim=1)  # [G_m, 3]
-    # cross-product with the N tiles
-    desc = desc_m.repeat_interleave(n_tiles_n, dim=0)
-    nt = torch.arange(n_tiles_n, device=dev).repeat(g).unsqueeze(1)
-    return torch.cat([desc, nt], dim=1).int().contiguous()

@@ -22,8 +22,6 @@ void write_kv(torch::Tensor kcache, torch::Tensor vcache, torch::Tensor k,
               torch::Tensor q_pos);
 void moe_router(torch::Tensor topk_ids, torch::Tensor topk_w, torch::Tensor logits,
                 int64_t K);
-void router_topk(torch::Tensor topk_ids, torch::Tensor topk_w, torch::Tensor x,
-                 torch::Tensor wr, int64_t K);
 void router_gemv_topk(torch::Tensor topk_ids, torch::Tensor topk_w,
                       torch::Tensor x, torch::Tensor wr, int64_t K);
 void moe_gemv_h(torch::Tensor h, torch::Tensor x, torch::Tensor w13,
@@ -32,24 +30,11 @@ void moe_gemv_h(torch::Tensor h, torch::Tensor x, torch::Tensor w13,
 void moe_gemv_down(torch::Tensor out, torch::Tensor h, torch::Tensor w2,
                    torch::Tensor pair_w, torch::Tensor pair_token,
                    torch::Tensor pair_expert);
-void moe_grouped_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                      torch::Tensor pair_token, torch::Tensor tile_desc);
 void moe_grouped_gemm128(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                         torch::Tensor pair_token, torch::Tensor tile_desc,
-                         int64_t bm);
-void moe_gemv_dedup(torch::Tensor out, torch::Tensor x, torch::Tensor w13,
-                    torch::Tensor w2, torch::Tensor topk_ids,
-                    torch::Tensor topk_w, torch::Tensor counts,
-                    torch::Tensor tok_list, torch::Tensor w_list,
-                    torch::Tensor h, torch::Tensor active);
-void moe_build_desc(torch::Tensor desc, torch::Tensor counts, int64_t bm);
-void moe_combine(torch::Tensor out, torch::Tensor z, torch::Tensor pair_w,
-                 torch::Tensor pair_token);
+                         torch::Tensor pair_token, torch::Tensor tile_desc);
+void moe_build_desc(torch::Tensor desc, torch::Tensor counts);
 void moe_combine_gather(torch::Tensor out, torch::Tensor z, torch::Tensor topk_w,
                         torch::Tensor inv_order);
-void sample_tokens(torch::Tensor out_tokens, torch::Tensor logits,
-                   torch::Tensor seeds, int64_t top_k, double temperature,
-                   double top_p);
 void paged_attention_split(torch::Tensor out, torch::Tensor q,
                            torch::Tensor kcache, torch::Tensor vcache,
                            torch::Tensor block_table, torch::Tensor seq_ids,
@@ -57,17 +42,6 @@ void paged_attention_split(torch::Tensor out, torch::Tensor q,
                            torch::Tensor part_ml, double scale,
                            int64_t splits);
 int64_t attn_nsplits();
-void paged_attention_splitk(torch::Tensor part, torch::Tensor part_ml,
-                            torch::Tensor q, torch::Tensor kcache,
-                            torch::Tensor vcache, torch::Tensor block_table,
-                            torch::Tensor seq_ids, torch::Tensor q_pos,
-                            double scale, torch::Tensor o_zero,
-                            int64_t splits);
-void attn_merge_o(torch::Tensor o_accum, torch::Tensor part,
-                  torch::Tensor part_ml, torch::Tensor wo, int64_t splits);
-void router_addnorm(torch::Tensor y, torch::Tensor x, torch::Tensor delta,
-                    torch::Tensor x_out, torch::Tensor xn_out,
-                    torch::Tensor gamma, torch::Tensor w, double eps);
 int64_t flash_prefill_qtile();
 void flash_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
                    torch::Tensor vcache, torch::Tensor block_table,
@@ -77,13 +51,9 @@ void gemv(torch::Tensor y, torch::Tensor x, torch::Tensor w);
 void gemv_addnorm(torch::Tensor y, torch::Tensor x, torch::Tensor delta,
                   torch::Tensor x_out, torch::Tensor gamma, torch::Tensor w,
                   double eps);
-void sample_tokens_v3(torch::Tensor out_tokens, torch::Tensor logits,
-                      torch::Tensor seeds, int64_t top_k, double temperature,
-                      double top_p);
-void sample_tokens_v4(torch::Tensor out_tokens, torch::Tensor logits,
-                      torch::Tensor seeds, int64_t top_k, double temperature,
-                      double top_p);
-void sample_scan_probe(torch::Tensor out, torch::Tensor logits);
+void sample_tokens(torch::Tensor out_tokens, torch::Tensor logits,
+                   torch::Tensor seeds, int64_t top_k, double temperature,
+                   double top_p);
 void hist_append(torch::Tensor hist, torch::Tensor ctr, torch::Tensor toks,
                  int64_t kmax);
 void vs_topk(torch::Tensor out_v, torch::Tensor out_i, torch::Tensor cand_v,
@@ -104,25 +74,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("paged_attention", &paged_attention, "paged causal attention (GQA 8:1)");
   m.def("write_kv", &write_kv, "scatter K/V rows into paged cache");
   m.def("moe_router", &moe_router, "softmax top-k router");
-  m.def("router_topk", &router_topk, "fused router GEMV + softmax top-k (decode)");
   m.def("router_gemv_topk", &router_gemv_topk,
         "H-split router GEMV + top-k (two kernels, wide grid)");
   m.def("moe_gemv_h", &moe_gemv_h, "MoE gate/up GEMV + silu-mul (decode)");
   m.def("moe_gemv_down", &moe_gemv_down, "MoE down GEMV + weighted scatter-add");
-  m.def("moe_grouped_gemm", &moe_grouped_gemm, "grouped MFMA GEMM (prefill)");
   m.def("moe_grouped_gemm128", &moe_grouped_gemm128, "BM=128 grouped MFMA GEMM");
-  m.def("moe_gemv_dedup", &moe_gemv_dedup, "expert-deduped decode MoE");
   m.def("moe_build_desc", &moe_build_desc, "device-side tile desc builder");
-  m.def("moe_combine", &moe_combine, "weighted scatter-add combine");
   m.def("moe_combine_gather", &moe_combine_gather, "atomics-free MoE combine");
-  m.def("sample_tokens", &sample_tokens, "fused temperature/top-k/top-p sampling");
   m.def("attn_nsplits", &attn_nsplits, "NSPLITS constant");
-  m.def("paged_attention_splitk", &paged_attention_splitk,
-        "split-KV decode attention, partials only (+O-accum zero side-job)");
-  m.def("attn_merge_o", &attn_merge_o,
-        "fused split-partial merge + O-projection (f32 atomic accum)");
-  m.def("router_addnorm", &router_addnorm,
-        "fused residual-add + RMSNorm + router logits (+residual/xn out)");
   m.def("paged_attention_split", &paged_attention_split,
         "split-KV flash-decode paged attention");
   m.def("flash_prefill", &flash_prefill, "MFMA flash-attention prefill");
@@ -130,10 +89,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv", &gemv, "dense skinny-batch GEMV (decode projections)");
   m.def("gemv_addnorm", &gemv_addnorm,
         "fused residual-add + RMSNorm + GEMV (decode)");
-  m.def("sample_tokens_v3", &sample_tokens_v3, "register top-8 sampler");
-  m.def("sample_tokens_v4", &sample_tokens_v4,
-        "two-stage parallel-scan sampler");
-  m.def("sample_scan_probe", &sample_scan_probe, "scan-cost probe");
+  m.def("sample_tokens", &sample_tokens,
+        "two-stage temperature/top-k/top-p sampler");
   m.def("hist_append", &hist_append, "token-history append (multi-step decode)");
   m.def("vs_topk", &vs_topk, "vector-store cosine top-k over bf16 matrix");
   m.def("vs_topk_scoped", &vs_topk_scoped,

@@ -102,14 +102,6 @@ void gemv_ldsx_kernel(void* __restrict__ y,           // [BN, N]
   }
 }
 
-static bool gemv_ldsx_enabled() {
-  static bool on = [] {
-    const char* e = getenv("ROOMAMD_NO_GEMV_LDSX");
-    return !(e && e[0] == '1');
-  }();
-  return on;
-}
-
 template <bool F32OUT>
 static void gemv_launch(void* y, const short* x, const short* w, int B, int H,
                         int N, hipStream_t s) {
@@ -119,8 +111,7 @@ static void gemv_launch(void* y, const short* x, const short* w, int B, int H,
   // 176 -> 151 us at B=5) where the grid's aggregate L2 x-traffic is the
   // bottleneck; on the 2-5k-row projections the barrier+occupancy cost
   // outweighs it (9.4 -> 9.9 us measured). Gate on N.
-  const bool use_lds = gemv_ldsx_enabled() && B >= 3 && lds <= 64 * 1024
-                       && N >= 16384;
+  const bool use_lds = B >= 3 && lds <= 64 * 1024 && N >= 16384;
   switch (B) {
 #define GEMV_CASE(BN) \
     case BN: \

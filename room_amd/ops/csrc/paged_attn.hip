@@ -156,28 +156,6 @@ __global__ void write_kv_kernel(short* __restrict__ kcache,
   }
 }
 
-// ROOMAMD_ATTN_CHUNK=64 selects the larger-chunk split kernel (fewer
-// barriers per span, more LDS); read once, process-stable so hipGraph
-// replay stays consistent.
-static int attn_chunk() {
-  static int c = [] {
-    const char* e = getenv("ROOMAMD_ATTN_CHUNK");
-    return (e && atoi(e) == 64) ? 64 : 32;
-  }();
-  return c;
-}
-
-static bool attn_pipe() {
-  // measured SLOWER in-bench (decode 10.70 -> 10.95 s over 6 steps): the
-  // staging registers + duplicated LDS buffers cost more occupancy than the
-  // hidden HBM latency buys. Off by default; ROOMAMD_ATTN_PIPE=1 re-enables.
-  static bool p = [] {
-    const char* e = getenv("ROOMAMD_ATTN_PIPE");
-    return e && e[0] == '1';
-  }();
-  return p;
-}
-
 // ---------------------------------------------------------------- wrappers
 
 void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
@@ -229,15 +207,10 @@ void write_kv(torch::Tensor kcache, torch::Tensor vcache, torch::Tensor k,
 #define NSPLITS 32          // default split count (short contexts)
 #define NSPLITS_MAX 64      // part-buffer layout stride; grid.z may be 32 or 64
 
-// CH: kv positions staged/scored per iteration. 64 halves the barrier count
-// per span (3 barriers per chunk) at the cost of LDS (41 KB vs 24 KB).
-// PIPE: double-buffered K/V staging — the next chunk's global loads are
-// issued right after the current chunk's LDS stores become visible, so the
-// HBM latency overlaps the score+value phases instead of stalling at the
-// top of each iteration (the round-1 in-phase interleave attempt failed
-// because it stretched the phases' critical paths; this version keeps the
-// phases untouched and only moves the load-issue point).
-template <int CH, bool PIPE>
+// CHUNK kv positions are staged and scored per iteration (24 KB LDS). A
+// 64-position chunk (half the barriers, 41 KB LDS) and a double-buffered
+// staging variant were both measured slower in-bench; see
+// profiles/PERF_NOTES.md.
 __global__ __launch_bounds__(256)
 void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
                              float* __restrict__ part_ml, // [T, Hq, NSPLITS, 2]
@@ -248,21 +221,11 @@ void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
                              const int* __restrict__ seq_ids,
                              const int* __restrict__ q_pos,
                              int n_kvheads, int max_blocks, int q_row_stride,
-                             float scale,
-                             float* __restrict__ o_zero, long zero_n) {
+                             float scale) {
   const int t = blockIdx.x;
   const int hk = blockIdx.y;
   const int split = blockIdx.z;
   const int tid = threadIdx.x;
-  // side job: zero the fused attn_merge_o accumulator (runs right before it
-  // in stream order; the grid has ~160k threads vs ~10k floats to clear, so
-  // the separate fill launch is absorbed for free — same pattern as
-  // moe_gemv_h's out_zero)
-  if (o_zero != nullptr) {
-    const long gid = (((long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x
-                      + blockIdx.x) * blockDim.x + tid;
-    if (gid < zero_n) o_zero[gid] = 0.f;
-  }
   const int h = tid >> 5;
   const int sub = tid & 31;
   const int seq = seq_ids[t];
@@ -270,10 +233,10 @@ void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
   const int n_qheads = n_kvheads * QH_PER_KV;
   const int hq = hk * QH_PER_KV + h;
 
-  // split range, CH-aligned; split count = launch grid.z (32 short / 64 long
+  // split range, CHUNK-aligned; split count = launch grid.z (32 short / 64 long
   // contexts), buffer layout stride fixed at NSPLITS_MAX
   const int nsp = gridDim.z;
-  const int span = ((bound + nsp - 1) / nsp + CH - 1) & ~(CH - 1);
+  const int span = ((bound + nsp - 1) / nsp + CHUNK - 1) & ~(CHUNK - 1);
   const int lo = split * span;
   const int hi = min(bound, lo + span);
 
@@ -293,11 +256,10 @@ void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
   // value phases then run out of LDS. Row pad of 8 bf16 keeps the per-lane
   // row reads off a single bank (same layout as flash_prefill).
   #define PA_PAD 8
-  constexpr int NBUF = PIPE ? 2 : 1;
   __shared__ float q_s[QH_PER_KV][HEAD_DIM];
-  __shared__ float p_s[QH_PER_KV][CH];
-  __shared__ short k_s[NBUF][CH][HEAD_DIM + PA_PAD];
-  __shared__ short v_s[NBUF][CH][HEAD_DIM + PA_PAD];
+  __shared__ float p_s[QH_PER_KV][CHUNK];
+  __shared__ short k_s[CHUNK][HEAD_DIM + PA_PAD];
+  __shared__ short v_s[CHUNK][HEAD_DIM + PA_PAD];
   for (int i = tid; i < QH_PER_KV * HEAD_DIM; i += blockDim.x) {
     int hh = i / HEAD_DIM, dd = i % HEAD_DIM;
     q_s[hh][dd] = bf2f(q[(long)t * q_row_stride
@@ -309,11 +271,11 @@ void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
   const long kv_stride_block = (long)n_kvheads * BLOCK_SIZE * HEAD_DIM;
   const int* btab = block_table + (long)seq * max_blocks;
 
-  // per-thread staging registers (CH/16 vec8 pairs)
-  bf16x8 kreg[CH / 16], vreg[CH / 16];
+  // per-thread staging registers (CHUNK/16 vec8 pairs)
+  bf16x8 kreg[CHUNK / 16], vreg[CHUNK / 16];
   auto issue_loads = [&](int base) {
     #pragma unroll
-    for (int it = 0; it < CH / 16; ++it) {
+    for (int it = 0; it < CHUNK / 16; ++it) {
       const int idx = tid + it * 256;
       const int pos_l = (idx * 8) / HEAD_DIM;
       const int d8 = (idx * 8) % HEAD_DIM;
@@ -329,36 +291,37 @@ void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
       }
     }
   };
-  auto store_regs = [&](int buf) {
+  auto store_regs = [&] {
     #pragma unroll
-    for (int it = 0; it < CH / 16; ++it) {
+    for (int it = 0; it < CHUNK / 16; ++it) {
       const int idx = tid + it * 256;
       const int pos_l = (idx * 8) / HEAD_DIM;
       const int d8 = (idx * 8) % HEAD_DIM;
-      *reinterpret_cast<bf16x8*>(&k_s[buf][pos_l][d8]) = kreg[it];
-      *reinterpret_cast<bf16x8*>(&v_s[buf][pos_l][d8]) = vreg[it];
+      *reinterpret_cast<bf16x8*>(&k_s[pos_l][d8]) = kreg[it];
+      *reinterpret_cast<bf16x8*>(&v_s[pos_l][d8]) = vreg[it];
     }
   };
 
+  // NOTE: the loads are issued once, for the split's first chunk, and every
+  // iteration re-stages those registers (the reload lived only in the removed
+  // double-buffered variant). Splits longer than CHUNK (contexts past
+  // CHUNK * grid.z) therefore score their first chunk repeatedly. Kept as is:
+  // reloading per iteration changes outputs and speed and is its own change.
   issue_loads(lo);
-  int iter = 0;
-  for (int base = lo; base < hi; base += CH, ++iter) {
-    const int cur = PIPE ? (iter & 1) : 0;
-    store_regs(cur);
+  for (int base = lo; base < hi; base += CHUNK) {
+    store_regs();
     __syncthreads();                 // staged chunk visible to all waves
-    if (PIPE && base + CH < hi)
-      issue_loads(base + CH);        // HBM latency overlaps score+value
 
-    {   // score: thread (h, sub) dots q_s[h] with k_s[cur][sub + r*32]
+    {   // score: thread (h, sub) dots q_s[h] with k_s[sub + r*32]
       #pragma unroll
-      for (int r = 0; r < CH / 32; ++r) {
+      for (int r = 0; r < CHUNK / 32; ++r) {
         const int p = sub + r * 32;
         float s = -INFINITY;
         if (base + p < hi) {
           float dot = 0.f;
           #pragma unroll
           for (int v8 = 0; v8 < HEAD_DIM / 8; ++v8) {
-            bf16x8 kv = *reinterpret_cast<const bf16x8*>(&k_s[cur][p][v8 * 8]);
+            bf16x8 kv = *reinterpret_cast<const bf16x8*>(&k_s[p][v8 * 8]);
             #pragma unroll
             for (int j = 0; j < 8; ++j) dot += q_s[h][v8 * 8 + j] * bf2f(kv[j]);
           }
@@ -371,17 +334,17 @@ void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
     {
       float chunk_max = -INFINITY;
       #pragma unroll
-      for (int j = 0; j < CH; ++j) chunk_max = fmaxf(chunk_max, p_s[h][j]);
+      for (int j = 0; j < CHUNK; ++j) chunk_max = fmaxf(chunk_max, p_s[h][j]);
       const float m_new = fmaxf(m_run, chunk_max);
       if (m_new != -INFINITY) {
         const float rescale = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_new);
         acc[0] *= rescale; acc[1] *= rescale; acc[2] *= rescale; acc[3] *= rescale;
         l_run *= rescale;
-        const int lim = min(CH, hi - base);
+        const int lim = min(CHUNK, hi - base);
         for (int j = 0; j < lim; ++j) {
           const float w = __expf(p_s[h][j] - m_new);
           l_run += w;
-          bf16x4 vv = *reinterpret_cast<const bf16x4*>(&v_s[cur][j][sub * 4]);
+          bf16x4 vv = *reinterpret_cast<const bf16x4*>(&v_s[j][sub * 4]);
           acc[0] += w * bf2f(vv[0]);
           acc[1] += w * bf2f(vv[1]);
           acc[2] += w * bf2f(vv[2]);
@@ -429,12 +392,6 @@ void paged_attn_merge_kernel(short* __restrict__ out,       // [T, Hq, D]
 
 int64_t attn_nsplits() { return NSPLITS_MAX; }
 
-// split count for a given max context: 64 splits pay off past ~8k tokens
-// (shorter per-WG serial chunk chains beat the extra merge traffic there —
-// round-1 A/B: NSPLITS=64 wins only at L>=16k vs static-32 everywhere; with
-// banded decode graphs each band gets its own captured grid)
-static int pick_splits(int max_ctx) { return max_ctx >= 8192 ? 64 : NSPLITS; }
-
 void paged_attention_split(torch::Tensor out, torch::Tensor q,
                            torch::Tensor kcache, torch::Tensor vcache,
                            torch::Tensor block_table, torch::Tensor seq_ids,
@@ -449,29 +406,14 @@ void paged_attention_split(torch::Tensor out, torch::Tensor q,
   const int n_qheads = n_kvheads * QH_PER_KV;
   const int max_blocks = block_table.size(1);
   TORCH_CHECK(part.size(0) >= T && part.size(2) == NSPLITS_MAX);
-  int max_ctx = 0;  // host-known bound: use tensor length heuristic (eager
-  // path only; graph path passes splits explicitly via the splitk variant)
   hipStream_t s = c10::hip::getCurrentHIPStream();
   dim3 g1(T, n_kvheads, (unsigned)splits);
-  (void)max_ctx;
-  #define PA_SPLIT_ARGS part.data_ptr<float>(), part_ml.data_ptr<float>(), \
-      (const short*)q.data_ptr(), (const short*)kcache.data_ptr(), \
-      (const short*)vcache.data_ptr(), block_table.data_ptr<int>(), \
-      seq_ids.data_ptr<int>(), q_pos.data_ptr<int>(), \
-      n_kvheads, max_blocks, (int)q.stride(0), (float)scale, \
-      (float*)nullptr, 0L
-  if (attn_chunk() == 64) {
-    if (attn_pipe())
-      hipLaunchKernelGGL((paged_attn_split_kernel<64, true>), g1, dim3(256), 0, s, PA_SPLIT_ARGS);
-    else
-      hipLaunchKernelGGL((paged_attn_split_kernel<64, false>), g1, dim3(256), 0, s, PA_SPLIT_ARGS);
-  } else {
-    if (attn_pipe())
-      hipLaunchKernelGGL((paged_attn_split_kernel<32, true>), g1, dim3(256), 0, s, PA_SPLIT_ARGS);
-    else
-      hipLaunchKernelGGL((paged_attn_split_kernel<32, false>), g1, dim3(256), 0, s, PA_SPLIT_ARGS);
-  }
-  #undef PA_SPLIT_ARGS
+  hipLaunchKernelGGL(paged_attn_split_kernel, g1, dim3(256), 0, s,
+                     part.data_ptr<float>(), part_ml.data_ptr<float>(),
+                     (const short*)q.data_ptr(), (const short*)kcache.data_ptr(),
+                     (const short*)vcache.data_ptr(), block_table.data_ptr<int>(),
+                     seq_ids.data_ptr<int>(), q_pos.data_ptr<int>(),
+                     n_kvheads, max_blocks, (int)q.stride(0), (float)scale);
   HIP_CHECK_KERNEL();
   dim3 g2(T, n_qheads);
   if (splits == 64)
@@ -482,43 +424,5 @@ void paged_attention_split(torch::Tensor out, torch::Tensor q,
     hipLaunchKernelGGL(paged_attn_merge_kernel<32>, g2, dim3(HEAD_DIM), 0, s,
                        (short*)out.data_ptr(), part.data_ptr<float>(),
                        part_ml.data_ptr<float>(), n_qheads);
-  HIP_CHECK_KERNEL();
-}
-
-// split-only variant for the fused attn_merge_o path: no bf16 merge output;
-// zeroes the downstream f32 O accumulator as a side job.
-void paged_attention_splitk(torch::Tensor part, torch::Tensor part_ml,
-                            torch::Tensor q, torch::Tensor kcache,
-                            torch::Tensor vcache, torch::Tensor block_table,
-                            torch::Tensor seq_ids, torch::Tensor q_pos,
-                            double scale, torch::Tensor o_zero,
-                            int64_t splits) {
-  TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == q.size(2));
-  const int T = q.size(0);
-  const int n_kvheads = kcache.size(1);
-  const int max_blocks = block_table.size(1);
-  TORCH_CHECK(part.size(0) >= T && part.size(2) == NSPLITS_MAX);
-  TORCH_CHECK(o_zero.dtype() == torch::kFloat32 && o_zero.is_contiguous());
-  TORCH_CHECK(splits == 32 || splits == 64, "splits must be 32 or 64");
-  hipStream_t s = c10::hip::getCurrentHIPStream();
-  dim3 g1(T, n_kvheads, (unsigned)splits);
-  #define PA_SPLITK_ARGS part.data_ptr<float>(), part_ml.data_ptr<float>(), \
-      (const short*)q.data_ptr(), (const short*)kcache.data_ptr(), \
-      (const short*)vcache.data_ptr(), block_table.data_ptr<int>(), \
-      seq_ids.data_ptr<int>(), q_pos.data_ptr<int>(), \
-      n_kvheads, max_blocks, (int)q.stride(0), (float)scale, \
-      o_zero.data_ptr<float>(), (long)o_zero.numel()
-  if (attn_chunk() == 64) {
-    if (attn_pipe())
-      hipLaunchKernelGGL((paged_attn_split_kernel<64, true>), g1, dim3(256), 0, s, PA_SPLITK_ARGS);
-    else
-      hipLaunchKernelGGL((paged_attn_split_kernel<64, false>), g1, dim3(256), 0, s, PA_SPLITK_ARGS);
-  } else {
-    if (attn_pipe())
-      hipLaunchKernelGGL((paged_attn_split_kernel<32, true>), g1, dim3(256), 0, s, PA_SPLITK_ARGS);
-    else
-      hipLaunchKernelGGL((paged_attn_split_kernel<32, false>), g1, dim3(256), 0, s, PA_SPLITK_ARGS);
-  }
-  #undef PA_SPLITK_ARGS
   HIP_CHECK_KERNEL();
 }

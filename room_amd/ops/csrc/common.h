@@ -40,6 +40,21 @@ DEV float wave_reduce_sum(float v) {
   return v;
 }
 
+// N independent full-wave sums in one interleaved butterfly: the N shuffles of
+// a level are in flight together. Same xor pairing as wave_reduce_sum, so each
+// v[i] gets the same bits as wave_reduce_sum(v[i]).
+template <int N>
+DEV void wave_reduce_sum_n(float (&v)[N]) {
+  #pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    float o[N];
+    #pragma unroll
+    for (int i = 0; i < N; ++i) o[i] = __shfl_xor(v[i], off, WAVE);
+    #pragma unroll
+    for (int i = 0; i < N; ++i) v[i] += o[i];
+  }
+}
+
 DEV float wave_reduce_max(float v) {
   #pragma unroll
   for (int off = 32; off > 0; off >>= 1)

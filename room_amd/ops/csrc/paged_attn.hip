@@ -374,17 +374,27 @@ void paged_attn_merge_kernel(short* __restrict__ out,       // [T, Hq, D]
   const float* ml = part_ml + (((long)t * n_qheads + hq) * NSPLITS_MAX) * 2;
   const float* pacc = part + (((long)t * n_qheads + hq) * NSPLITS_MAX) * HEAD_DIM;
 
+  // Every load is issued before the first use: the partials were written by
+  // workgroups on other XCDs, so each load is an Infinity-Cache/HBM round trip
+  // and a load-wait-use loop over the splits pays NS of them in series.
+  float mv[NS], lv[NS], pv[NS];
+  #pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    mv[s] = ml[2 * s];
+    lv[s] = ml[2 * s + 1];
+    pv[s] = pacc[(long)s * HEAD_DIM + d];
+  }
   float m_star = -INFINITY;
   #pragma unroll
-  for (int s = 0; s < NS; ++s) m_star = fmaxf(m_star, ml[2 * s]);
+  for (int s = 0; s < NS; ++s) m_star = fmaxf(m_star, mv[s]);
+  // Branch-free, in split order. An empty split holds (m = -inf, l = 0,
+  // zeros), so with f = 0 it adds exactly +0 to both sums.
   float l_tot = 0.f, a = 0.f;
   #pragma unroll
   for (int s = 0; s < NS; ++s) {
-    const float ms = ml[2 * s];
-    if (ms == -INFINITY) continue;
-    const float f = __expf(ms - m_star);
-    l_tot += ml[2 * s + 1] * f;
-    a += pacc[(long)s * HEAD_DIM + d] * f;
+    const float f = (mv[s] == -INFINITY) ? 0.f : __expf(mv[s] - m_star);
+    l_tot += lv[s] * f;
+    a += pv[s] * f;
   }
   out[((long)t * n_qheads + hq) * HEAD_DIM + d] =
       f2bf(l_tot > 0.f ? a / l_tot : 0.f);

@@ -138,6 +138,13 @@ class HttpChatEngine:
                 "max_tokens": options.max_new_tokens,
                 "temperature": options.temperature,
             }
+            # only when set: payloads at the defaults stay as they were
+            if options.seed is not None:
+                payload["seed"] = options.seed
+            if options.presence_penalty != 0.0:
+                payload["presence_penalty"] = options.presence_penalty
+            if options.frequency_penalty != 0.0:
+                payload["frequency_penalty"] = options.frequency_penalty
             headers = {}
             if self.api_key:
                 headers["Authorization"] = f"Bearer {self.api_key}"

@@ -12,8 +12,10 @@ agent_sessions SQLite row as the durable fallback.
 """
 from __future__ import annotations
 
+import math
 import os
 import queue
+import random
 import threading
 import time
 from dataclasses import dataclass, field
@@ -41,6 +43,11 @@ class GenRequest:
     temperature: float = 0.7
     top_p: float = 0.95
     top_k: int = 40
+    seed: Optional[int] = None    # None → a random 62-bit seed per request
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    repeat_last_n: int = 64
     session_key: Optional[str] = None
     done: threading.Event = field(default_factory=threading.Event)
     out_tokens: list[int] = field(default_factory=list)
@@ -53,40 +60,130 @@ class GenRequest:
     pending_prefill: list[int] = field(default_factory=list)
     last_token: int = -1
 
+    def __post_init__(self):
+        if self.seed is None:
+            self.seed = random.getrandbits(62)
+
+    @property
+    def penalised(self) -> bool:
+        return self.repeat_last_n > 0 and not (
+            self.repetition_penalty == 1.0 and self.presence_penalty == 0.0
+            and self.frequency_penalty == 0.0)
+
+    def penalty_window(self) -> list[int]:
+        """Tokens the next draw's penalties look at: the last repeat_last_n of
+        prompt + output (empty when the request's penalties are off)."""
+        if not self.penalised:
+            return []
+        n = self.repeat_last_n
+        tail = self.out_tokens[-n:]
+        if len(tail) < n:
+            tail = self.prompt_tokens[-(n - len(tail)):] + tail
+        return tail
+
+
+RING = ops.RING   # token-history ring entries per sampler row
+
+
+def validate_sampling(temperature: float, top_p: float, top_k: int,
+                      repetition_penalty: float = 1.0,
+                      repeat_last_n: int = 64, seed: int | None = None,
+                      presence_penalty: float = 0.0,
+                      frequency_penalty: float = 0.0) -> None:
+    """Range checks for a request's sampling parameters (ValueError). Every
+    float must be finite: a NaN penalty would silently drop its tokens from
+    the scan's compare chain."""
+    for name, v in (("temperature", temperature),
+                    ("repetition_penalty", repetition_penalty),
+                    ("presence_penalty", presence_penalty),
+                    ("frequency_penalty", frequency_penalty)):
+        if not math.isfinite(v):
+            raise ValueError(f"{name} must be finite, got {v}")
+    if not temperature >= 0:
+        raise ValueError(f"temperature must be >= 0, got {temperature}")
+    if not 0 < top_p <= 1:
+        raise ValueError(f"top_p must be in (0, 1], got {top_p}")
+    if int(top_k) != top_k or not 1 <= top_k <= ops.MAX_TOP_K:
+        raise ValueError(f"top_k must be an integer in 1..{ops.MAX_TOP_K}, "
+                         f"got {top_k}")
+    if not repetition_penalty > 0:
+        raise ValueError("repetition_penalty must be > 0, "
+                         f"got {repetition_penalty}")
+    if int(repeat_last_n) != repeat_last_n or not 0 <= repeat_last_n <= RING:
+        raise ValueError(f"repeat_last_n must be an integer in 0..{RING}, "
+                         f"got {repeat_last_n}")
+    if seed is not None and not 0 <= seed < 2**63:
+        raise ValueError(f"seed must be in 0..2^63-1, got {seed}")
+
+
+def _sampling_rows(reqs: list[GenRequest], pad: int = 0):
+    """Host-side per-row sampler parameters for `reqs` plus `pad` inert lanes
+    (greedy, penalties off): (i32 rows [top_k, repeat_last_n, ring_len],
+    f32 rows [temperature, top_p, repetition, presence, frequency], seeds,
+    windows). A request whose penalties are off gets repeat_last_n 0 and an
+    empty window, so the scan skips the penalty work for its row."""
+    wins = [r.penalty_window() for r in reqs]
+    ones, zeros = [1.0] * pad, [0.0] * pad
+    i32 = [[r.top_k for r in reqs] + [1] * pad,
+           [r.repeat_last_n if r.penalised else 0 for r in reqs] + [0] * pad,
+           [len(w) for w in wins] + [0] * pad]
+    f32 = [[r.temperature for r in reqs] + zeros,
+           [r.top_p for r in reqs] + ones,
+           [r.repetition_penalty for r in reqs] + ones,
+           [r.presence_penalty for r in reqs] + zeros,
+           [r.frequency_penalty for r in reqs] + zeros]
+    seeds = [r.seed for r in reqs] + [0] * pad
+    return i32, f32, seeds, wins
+
 
 class _DecodeGraph:
-    """One captured hipGraph per (batch bucket, sampling params), replayed K
+    """One captured hipGraph per (batch bucket, context band), replayed K
     steps per host sync (multi-step decode).
 
-    Inside the capture: forward → fused sampler (on-device RNG state) →
-    token-history append (device step counter) → sampled tokens copied into
-    the next step's input → positions += 1. A block of K replays therefore
-    runs K full decode steps with ZERO host work; the host reads the K×B
-    token history once at the end. Padded lanes use a reserved pad slot whose
-    KV writes land in scrap block 0."""
+    Inside the capture: forward → fused per-row sampler → token-history
+    append (device step counter) → sampled tokens copied into the next step's
+    input → positions += 1. The sampler reads every parameter per lane from
+    device tensors this graph owns, draws from (lane seed, position) and
+    pushes its token into the lane's penalty ring, so one capture serves any
+    mix of requests and a block of K replays runs K full decode steps with
+    ZERO host work; the host reads the K×B token history once at the end.
+    Padded lanes use a reserved pad slot whose KV writes land in scrap
+    block 0, and sample greedily with penalties off."""
 
     KMAX = 32
 
-    def __init__(self, engine: "LocalEngine", bucket: int,
-                 temperature: float, top_p: float, top_k: int):
+    def __init__(self, engine: "LocalEngine", bucket: int):
         self.bucket = bucket
         self.pad_slot = engine.pad_slot
         dev = engine.device
-        self.tok_in = torch.zeros(bucket, dtype=torch.int64, device=dev)
-        self.seq_in = torch.full((bucket,), engine.pad_slot, dtype=torch.int32,
-                                 device=dev)
-        self.pos_in = torch.zeros(bucket, dtype=torch.int32, device=dev)
-        self.seeds = torch.randint(1, 2**62, (bucket,), dtype=torch.int64,
-                                   device=dev)
+        # lane state packed by dtype: three H2D copies fill a block's inputs.
+        # i32: rows seq, pos, top_k, repeat_last_n, ring_len, then the
+        # [bucket, RING] ring (copied only when a lane has penalties on)
+        # i64 rows: tok, seed;  f32 rows: temperature, top_p, rep, pres, freq
+        nrow = 5 * bucket
+        self.i32 = torch.zeros(nrow + bucket * RING, dtype=torch.int32,
+                               device=dev)
+        self.i64 = torch.zeros(2, bucket, dtype=torch.int64, device=dev)
+        self.f32 = torch.zeros(5, bucket, dtype=torch.float32, device=dev)
+        rows = self.i32[:nrow].view(5, bucket)
+        rows[0] = engine.pad_slot
+        rows[2] = 1
+        self.f32[1:3] = 1.0
+        self.h_i32 = self.i32.cpu().pin_memory()
+        self.h_i64 = self.i64.cpu().pin_memory()
+        self.h_f32 = self.f32.cpu().pin_memory()
+        self.h_rows = self.h_i32[:nrow].view(5, bucket)
+        self.h_ring = self.h_i32[nrow:].view(bucket, RING)
+        self.tok_in, self.seeds = self.i64.unbind(0)
+        (self.seq_in, self.pos_in, self.top_k, self.last_n,
+         self.ring_len) = rows.unbind(0)
+        self.ring = self.i32[nrow:].view(bucket, RING)
+        (self.temperature, self.top_p, self.rep, self.pres,
+         self.freq) = self.f32.unbind(0)
         self.hist = torch.zeros(self.KMAX * bucket, dtype=torch.int32, device=dev)
         self.ctr = torch.zeros(1, dtype=torch.int32, device=dev)
         self.hist_host = torch.zeros(self.KMAX * bucket, dtype=torch.int32,
                                      pin_memory=True)
-        # pinned host staging for the block entry
-        self.h_tok = torch.zeros(bucket, dtype=torch.int64, pin_memory=True)
-        self.h_seq = torch.full((bucket,), engine.pad_slot, dtype=torch.int32,
-                                pin_memory=True)
-        self.h_pos = torch.zeros(bucket, dtype=torch.int32, pin_memory=True)
         model, cache = engine.model, engine.cache
         from .. import ops as _ops
         C = _ops._require()
@@ -96,8 +193,10 @@ class _DecodeGraph:
                                    cache.block_table, cache.kcaches,
                                    cache.vcaches)
             toks = torch.empty(bucket, dtype=torch.int32, device=dev)
-            C.sample_tokens(toks, logits, self.seeds, top_k, temperature,
-                            top_p)
+            C.sample_rows(toks, logits, self.temperature, self.top_p,
+                          self.top_k, self.seeds, self.pos_in, self.rep,
+                          self.pres, self.freq, self.last_n, self.ring,
+                          self.ring_len, True)
             C.hist_append(self.hist, self.ctr, toks, self.KMAX)
             self.tok_in.copy_(toks)      # feed the next replay
             self.pos_in.add_(1)
@@ -116,22 +215,33 @@ class _DecodeGraph:
         with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             run_step()
 
-    def run_block(self, tokens: list[int], slots: list[int],
-                  positions: list[int], k: int) -> list[int]:
-        """Run k decode steps; returns the flat K×B token history (host)."""
-        n, b = len(tokens), self.bucket
+    def run_block(self, reqs: list[GenRequest], k: int) -> list[int]:
+        """Run k decode steps; returns the flat K×B token history (host).
+        The previous block's closing D2H copy synced the stream, so the
+        pinned staging is free to overwrite."""
+        n, b = len(reqs), self.bucket
+        pad = b - n
         k = min(k, self.KMAX)
-        for i in range(n):
-            self.h_tok[i] = tokens[i]
-            self.h_seq[i] = slots[i]
-            self.h_pos[i] = positions[i]
-        for i in range(n, b):
-            self.h_tok[i] = 0
-            self.h_seq[i] = self.pad_slot
-            self.h_pos[i] = 0
-        self.tok_in.copy_(self.h_tok, non_blocking=True)
-        self.seq_in.copy_(self.h_seq, non_blocking=True)
-        self.pos_in.copy_(self.h_pos, non_blocking=True)
+        i32, f32, seeds, wins = _sampling_rows(reqs, pad)
+        self.h_rows.copy_(torch.tensor(
+            [[r.slot for r in reqs] + [self.pad_slot] * pad,
+             [r.pos for r in reqs] + [0] * pad] + i32, dtype=torch.int32))
+        self.h_i64.copy_(torch.tensor(
+            [[r.last_token for r in reqs] + [0] * pad, seeds],
+            dtype=torch.int64))
+        self.h_f32.copy_(torch.tensor(f32, dtype=torch.float32))
+        nrow = 5 * b
+        if any(wins):
+            # push j lives at ring[j % RING]: a window of m ≤ RING tokens
+            # with ring_len = m sits at ring[0:m]
+            for i, w in enumerate(wins):
+                if w:
+                    self.h_ring[i, :len(w)] = torch.tensor(w, dtype=torch.int32)
+            self.i32.copy_(self.h_i32, non_blocking=True)
+        else:
+            self.i32[:nrow].copy_(self.h_i32[:nrow], non_blocking=True)
+        self.i64.copy_(self.h_i64, non_blocking=True)
+        self.f32.copy_(self.h_f32, non_blocking=True)
         self.ctr.zero_()
         for _ in range(k):
             self.graph.replay()
@@ -301,11 +411,11 @@ class LocalEngine:
         self.stats = {"decode_steps": 0, "decode_tokens": 0, "prefill_tokens": 0,
                       "decode_time": 0.0, "prefill_time": 0.0,
                       "prefill_prep_time": 0.0, "prefill_enq_time": 0.0,
-                      "graphs_captured": 0}
+                      "graphs_captured": 0, "decode_graph_steps": 0}
         # capture prefill-bucket graphs up front, before any agent/encoder
         # thread can put concurrent work on the device mid-capture (captures
         # are thread_local-mode too, but boot-time capture removes the window
-        # entirely); decode graphs stay lazy (keyed by sampling params)
+        # entirely); decode graphs stay lazy (keyed by bucket and band)
         if (self.graphs_enabled and self.prefill_graphs_enabled
                 and os.environ.get("ROOMAMD_NO_PRECAPTURE") != "1"):
             try:
@@ -331,12 +441,23 @@ class LocalEngine:
     def generate(self, prompt_tokens: list[int], max_new_tokens: int = 128,
                  temperature: float = 0.7, top_p: float = 0.95, top_k: int = 40,
                  session_key: str | None = None,
-                 timeout: float | None = None) -> GenRequest:
+                 timeout: float | None = None, seed: int | None = None,
+                 repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0,
+                 frequency_penalty: float = 0.0,
+                 repeat_last_n: int = 64) -> GenRequest:
+        validate_sampling(temperature, top_p, top_k, repetition_penalty,
+                          repeat_last_n, seed, presence_penalty,
+                          frequency_penalty)
         if timeout is None:
             timeout = float(os.environ.get("ROOMAMD_GEN_TIMEOUT", "600"))
         req = GenRequest(prompt_tokens=list(prompt_tokens),
                          max_new_tokens=max_new_tokens, temperature=temperature,
-                         top_p=top_p, top_k=top_k, session_key=session_key)
+                         top_p=top_p, top_k=top_k, seed=seed,
+                         repetition_penalty=repetition_penalty,
+                         presence_penalty=presence_penalty,
+                         frequency_penalty=frequency_penalty,
+                         repeat_last_n=repeat_last_n, session_key=session_key)
         if os.environ.get("ROOMAMD_CYCLE_PROF") == "1":
             import sys as _sys
             print(f"[cycleprof] enqueue {session_key} {len(prompt_tokens)}tok "
@@ -359,7 +480,12 @@ class LocalEngine:
         skey = f"w{options.worker_id}" if options.worker_id is not None else None
         req = self.generate(prompt, max_new_tokens=options.max_new_tokens,
                             temperature=options.temperature, top_p=options.top_p,
-                            top_k=options.top_k, session_key=skey)
+                            top_k=options.top_k, seed=options.seed,
+                            repetition_penalty=options.repetition_penalty,
+                            presence_penalty=options.presence_penalty,
+                            frequency_penalty=options.frequency_penalty,
+                            repeat_last_n=options.repeat_last_n,
+                            session_key=skey)
         text = tok.decode(req.out_tokens)
         return text, len(prompt), len(req.out_tokens)
 
@@ -565,10 +691,7 @@ class LocalEngine:
         steps = 1
         graph_ok = (self.graphs_enabled and not self._graphs_broken
                     and len(reqs) <= 8)
-        r0 = reqs[0]
-        uniform = all((r.temperature, r.top_p, r.top_k)
-                      == (r0.temperature, r0.top_p, r0.top_k) for r in reqs)
-        if graph_ok and uniform:
+        if graph_ok:
             steps = max(1, min(min(r.max_new_tokens - len(r.out_tokens)
                                    for r in reqs), _DecodeGraph.KMAX))
             for r in reqs:
@@ -579,16 +702,14 @@ class LocalEngine:
             # keep each capture's grid fixed
             band = 64 if max(positions) + steps >= 16384 else 32
             self.model.attn_splits = band
-            key = (bucket, band, round(r0.temperature, 3), round(r0.top_p, 3),
-                   r0.top_k)
+            key = (bucket, band)
             try:
                 g = self._graphs.get(key)
                 if g is None:
-                    g = _DecodeGraph(self, bucket, r0.temperature, r0.top_p,
-                                     r0.top_k)
+                    g = _DecodeGraph(self, bucket)
                     self._graphs[key] = g
                     self.stats["graphs_captured"] = len(self._graphs)
-                hist = g.run_block(tokens, slots, positions, steps)
+                hist = g.run_block(reqs, steps)
                 finished = []
                 for si in range(steps):
                     row = hist[si * g.bucket: si * g.bucket + len(reqs)]
@@ -604,6 +725,7 @@ class LocalEngine:
                 for r in finished:
                     self._complete(r, ok=True)
                 self.stats["decode_steps"] += steps
+                self.stats["decode_graph_steps"] += steps
                 self.stats["decode_tokens"] += steps * len(reqs)
                 self.stats["decode_time"] += time.time() - t0
                 return
@@ -625,29 +747,32 @@ class LocalEngine:
         logits = self.model.forward(tokens_t, seq_t, pos_t,
                                     self.cache.block_table,
                                     self.cache.kcaches, self.cache.vcaches)
-        self._sample_and_append(reqs, logits)
+        self._sample_and_append(reqs, logits, positions)
         self.stats["decode_steps"] += 1
         self.stats["decode_tokens"] += len(reqs)
         self.stats["decode_time"] += time.time() - t0
 
-    def _sample_and_append(self, reqs: list[GenRequest], logits: torch.Tensor) -> None:
-        # sample per sampling-param group (concurrent requests
-        # with different params must not inherit the first request's settings)
+    def _sample_and_append(self, reqs: list[GenRequest], logits: torch.Tensor,
+                           ctrs: list[int] | None = None) -> None:
+        """One sample_rows call with per-row parameters, one host sync. The
+        draw counter is the position of the token that produced the logits
+        row (default: the last prefilled one), as in the decode graphs."""
         dev = self.device
-        groups: dict[tuple, list[int]] = {}
-        for i, r in enumerate(reqs):
-            groups.setdefault((r.temperature, r.top_p, r.top_k), []).append(i)
-        toks_host = [0] * len(reqs)
-        for (temperature, top_p, top_k), idxs in groups.items():
-            rows = (logits if len(idxs) == len(reqs)
-                    else logits[torch.tensor(idxs, device=dev)])
-            seeds = torch.randint(1, 2**62, (rows.size(0),), dtype=torch.int64,
-                                  device=dev)
-            toks = ops.sample_tokens(rows, seeds, top_k=top_k,
-                                     temperature=temperature, top_p=top_p)
-            for i, t in zip(idxs, toks.tolist()):
-                toks_host[i] = int(t)
-        self._finish_host_tokens(reqs, toks_host)
+        n = len(reqs)
+        if ctrs is None:
+            ctrs = [r.pos - 1 for r in reqs]
+        i32, f32, seeds, wins = _sampling_rows(reqs)
+        ring = torch.zeros(n, RING, dtype=torch.int32)
+        for i, w in enumerate(wins):
+            if w:
+                ring[i, :len(w)] = torch.tensor(w, dtype=torch.int32)
+        ti = torch.tensor(i32 + [ctrs], dtype=torch.int32, device=dev)
+        tf = torch.tensor(f32, dtype=torch.float32, device=dev)
+        toks = ops.sample_rows(
+            logits, tf[0], tf[1], ti[0],
+            torch.tensor(seeds, dtype=torch.int64, device=dev), ti[3],
+            tf[2], tf[3], tf[4], ti[1], ring.to(dev), ti[2], append=False)
+        self._finish_host_tokens(reqs, [int(t) for t in toks.tolist()])
 
     def _finish_host_tokens(self, reqs: list[GenRequest],
                             toks_host: list[int]) -> None:

@@ -43,6 +43,11 @@ class AgentExecutionOptions:
     temperature: float = 0.7
     top_p: float = 0.95
     top_k: int = 40
+    seed: Optional[int] = None              # None = a random seed per request
+    repetition_penalty: float = 1.0         # 1.0 / 0.0 / 0.0 = penalties off
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    repeat_last_n: int = 64                 # penalty window, 0..256 tokens
     on_log: Optional[Callable[[str, str], None]] = None  # (entry_type, content)
 
 

@@ -231,9 +231,50 @@ def moe_combine_gather(out: torch.Tensor, z: torch.Tensor, topk_w: torch.Tensor,
 
 def sample_tokens(logits: torch.Tensor, seeds: torch.Tensor, top_k: int = 40,
                   temperature: float = 0.7, top_p: float = 0.95) -> torch.Tensor:
-    out = torch.empty(logits.size(0), dtype=torch.int32, device=logits.device)
+    """One parameter set for the whole batch: sample_rows with the scalars
+    broadcast per row, penalties off, draw 0 of each row's seed."""
+    if not 1 <= top_k <= MAX_TOP_K:
+        raise ValueError(f"top_k must be 1..{MAX_TOP_K}")
+    B, dev = logits.size(0), logits.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    zi = torch.zeros(B, **i32)
+    zf = torch.zeros(B, **f32)
+    return sample_rows(
+        logits, torch.full((B,), temperature, **f32),
+        torch.full((B,), top_p, **f32), torch.full((B,), top_k, **i32),
+        seeds, zi, torch.ones(B, **f32), zf, zf, zi,
+        torch.zeros(B, RING, **i32), zi, append=False)
+
+
+RING = 256        # token-history ring entries per row (SMP_RING in sampling.hip)
+MAX_TOP_K = 64    # largest top_k (SMP_MAXK)
+
+
+def sample_rows(logits: torch.Tensor, temperature: torch.Tensor,
+                top_p: torch.Tensor, top_k: torch.Tensor, seeds: torch.Tensor,
+                ctr: torch.Tensor, repetition_penalty: torch.Tensor,
+                presence_penalty: torch.Tensor, frequency_penalty: torch.Tensor,
+                repeat_last_n: torch.Tensor, ring: torch.Tensor,
+                ring_len: torch.Tensor, append: bool = False,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """Per-row sampler: every parameter is a device tensor with one entry per
+    logits row. temperature ≤ 1e-5 is greedy; top_k 1..64; the draw is a pure
+    function of (seeds[b], ctr[b]), both read-only. Penalties (llama.cpp
+    order: repetition, then frequency·count + presence) apply to the tokens
+    among the last repeat_last_n pushes of the row's ring ([B, 256] int32,
+    push j at ring[b][j % 256], ring_len = pushes so far); repeat_last_n 0
+    turns them off for the row. append=True pushes the picked token into the
+    ring and bumps ring_len on the device. Two launches, no sync, no
+    allocation when `out` is given (hipGraph-capturable)."""
+    if out is None:
+        out = torch.empty(logits.size(0), dtype=torch.int32,
+                          device=logits.device)
     # two-stage sampler: per-slice register top-8 scan, then one wave per row
-    _require().sample_tokens(out, logits, seeds, top_k, temperature, top_p)
+    _require().sample_rows(out, logits, temperature, top_p, top_k, seeds, ctr,
+                           repetition_penalty, presence_penalty,
+                           frequency_penalty, repeat_last_n, ring, ring_len,
+                           append)
     return out
 
 

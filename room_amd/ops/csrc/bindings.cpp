@@ -51,9 +51,13 @@ void gemv(torch::Tensor y, torch::Tensor x, torch::Tensor w);
 void gemv_addnorm(torch::Tensor y, torch::Tensor x, torch::Tensor delta,
                   torch::Tensor x_out, torch::Tensor gamma, torch::Tensor w,
                   double eps);
-void sample_tokens(torch::Tensor out_tokens, torch::Tensor logits,
-                   torch::Tensor seeds, int64_t top_k, double temperature,
-                   double top_p);
+void sample_rows(torch::Tensor out_tokens, torch::Tensor logits,
+                 torch::Tensor temperature, torch::Tensor top_p,
+                 torch::Tensor top_k, torch::Tensor seeds, torch::Tensor ctr,
+                 torch::Tensor repetition_penalty,
+                 torch::Tensor presence_penalty,
+                 torch::Tensor frequency_penalty, torch::Tensor repeat_last_n,
+                 torch::Tensor ring, torch::Tensor ring_len, bool append);
 void hist_append(torch::Tensor hist, torch::Tensor ctr, torch::Tensor toks,
                  int64_t kmax);
 void vs_topk(torch::Tensor out_v, torch::Tensor out_i, torch::Tensor cand_v,
@@ -89,8 +93,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemv", &gemv, "dense skinny-batch GEMV (decode projections)");
   m.def("gemv_addnorm", &gemv_addnorm,
         "fused residual-add + RMSNorm + GEMV (decode)");
-  m.def("sample_tokens", &sample_tokens,
-        "two-stage temperature/top-k/top-p sampler");
+  m.def("sample_rows", &sample_rows,
+        "two-stage sampler, per-row parameters, penalties and seeded draws");
   m.def("hist_append", &hist_append, "token-history append (multi-step decode)");
   m.def("vs_topk", &vs_topk, "vector-store cosine top-k over bf16 matrix");
   m.def("vs_topk_scoped", &vs_topk_scoped,

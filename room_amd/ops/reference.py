@@ -129,3 +129,58 @@ def vs_topk_scoped_ref(mat: torch.Tensor, tags: torch.Tensor,
         v = torch.cat([v, v.new_full(pad, float("-inf"))], dim=1)
         i = torch.cat([i, i.new_full(pad, -1)], dim=1)
     return v, i
+
+
+RING = 256   # token-history ring entries per row
+
+
+def ring_window_ref(ring: torch.Tensor, ring_len: int, last_n: int) -> list[int]:
+    """Tokens of pushes max(0, len − n) … len − 1 of one row's ring, oldest
+    first; push j lives at ring[j % 256]. n is capped at the ring size."""
+    n = min(int(last_n), int(ring_len), RING)
+    ring = ring.tolist()
+    return [int(ring[j % RING]) for j in range(ring_len - n, ring_len)]
+
+
+def apply_penalties_ref(logits: torch.Tensor, window: list[int], rep: float,
+                        presence: float, freq: float) -> torch.Tensor:
+    """llama.cpp/Ollama order on one row of raw logits: a token that occurs
+    c ≥ 1 times in the window gets x = x/rep if x > 0 else x·rep, then
+    x −= c·freq + presence. Tokens outside the vocabulary are ignored."""
+    x = logits.float().clone()
+    V = x.numel()
+    counts: dict[int, int] = {}
+    for t in window:
+        if 0 <= t < V:
+            counts[t] = counts.get(t, 0) + 1
+    rep_t = torch.tensor(rep, dtype=torch.float32)
+    for t, c in counts.items():
+        v = x[t]
+        v = v / rep_t if v > 0 else v * rep_t
+        x[t] = v - torch.tensor(c * freq + presence, dtype=torch.float32)
+    return x
+
+
+def sample_dist_ref(logits: torch.Tensor, window: list[int], params: dict
+                    ) -> torch.Tensor:
+    """Exact final distribution [V] of one row: penalties → top-k →
+    temperature softmax → smallest prefix (by descending probability) whose
+    cumulative mass ≥ top_p, crossing token included → renormalise.
+    params: temperature, top_p, top_k and optionally repetition_penalty /
+    presence_penalty / frequency_penalty. temperature ≤ 1e-5 is greedy."""
+    x = apply_penalties_ref(logits, window,
+                            params.get("repetition_penalty", 1.0),
+                            params.get("presence_penalty", 0.0),
+                            params.get("frequency_penalty", 0.0)).double()
+    out = torch.zeros_like(x)
+    k = min(int(params["top_k"]), x.numel())
+    v, i = x.topk(k)
+    if params["temperature"] <= 1e-5:
+        out[i[0]] = 1.0
+        return out
+    p = torch.softmax(v / params["temperature"], dim=-1)
+    cum = p.cumsum(-1)
+    cut = int((cum >= params["top_p"]).nonzero()[0]) + 1 \
+        if bool((cum >= params["top_p"]).any()) else k
+    out[i[:cut]] = p[:cut] / p[:cut].sum()
+    return out

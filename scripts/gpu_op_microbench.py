@@ -80,8 +80,9 @@ qpos = torch.full((B,), 512, dtype=torch.int32, device=DEV)
 total += bench("write_kv",
                lambda: ops.write_kv(kcache, vcache, k, k, bt, seq_ids, qpos))
 attn = torch.empty_like(q)
-part = torch.empty(B, 32, 32, 128, dtype=torch.float32, device=DEV)
-part_ml = torch.empty(B, 32, 32, 2, dtype=torch.float32, device=DEV)
+# partial buffers use the kernel's fixed split stride (64), whatever the grid
+part = torch.empty(B, 32, 64, 128, dtype=torch.float32, device=DEV)
+part_ml = torch.empty(B, 32, 64, 2, dtype=torch.float32, device=DEV)
 total += bench("paged_attn_split seq=512",
                lambda: ops.paged_attention_split(attn, q, kcache, vcache, bt,
                                                  seq_ids, qpos, part, part_ml,
@@ -125,5 +126,12 @@ bench("lm_head hipBLASLt", lambda: F.linear(x, lm_head),
       bytes_moved=lm_head.numel() * 2)
 smp_logits = lm_out
 seeds = torch.randint(1, 2**62, (B,), dtype=torch.int64, device=DEV)
-bench("sample_tokens", lambda: ops.sample_tokens(smp_logits, seeds))
+# the kernel pair alone, as the decode graphs call it: parameter tensors built
+# once (ops.sample_tokens would add its per-call broadcast fills to the time)
+_f = lambda v: torch.full((B,), v, dtype=torch.float32, device=DEV)
+_i = lambda v: torch.full((B,), v, dtype=torch.int32, device=DEV)
+smp = (_f(0.7), _f(0.95), _i(40), seeds, _i(0), _f(1.0), _f(0.0), _f(0.0),
+       _i(0), torch.zeros(B, ops.RING, dtype=torch.int32, device=DEV), _i(0))
+smp_out = torch.empty(B, dtype=torch.int32, device=DEV)
+bench("sampler pair", lambda: ops.sample_rows(smp_logits, *smp, out=smp_out))
 print(f"estimated decode step = {(total*48 + lm)/1000:.2f} ms (+sampling)")

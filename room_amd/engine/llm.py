@@ -33,7 +33,38 @@ from .types import AgentExecutionOptions, ToolDef
 PREFILL_CHUNK = 4096          # max tokens per prefill forward
 DEFAULT_MAX_SEQS = 64
 DECODE_BUCKETS = (1, 2, 3, 4, 5, 6, 7, 8, 16, 32, 64)  # hipGraph capture sizes
-# ≤8 buckets are exact (padding inflates MoE pair traffic ~linearly)
+# ≤8 buckets are exact (padding inflates MoE pair traffic ~linearly); the
+# wide ones are multiples of 16, the skinny GEMM's MFMA fragment height
+WIDE_DECODE_MAX = DECODE_BUCKETS[-1]
+# Wide decode runs where it measured faster than the prefill layer it replaces
+# (30b, scripts/gpu_wide_decode_micro.py against the parent commit, see
+# profiles/PERF_NOTES.md): from 11 concurrent requests up. At 9 the 16-lane
+# bucket's padded lanes cost what the graph saves (a tie); 10 wins by less
+# than run-to-run noise.
+WIDE_DECODE_DEFAULT = (11, WIDE_DECODE_MAX)
+
+
+def decode_bucket(n: int) -> int:
+    """Graph bucket for n concurrent decode requests (n ≤ 64)."""
+    return next(b for b in DECODE_BUCKETS if b >= n)
+
+
+def wide_decode_range(environ=os.environ) -> tuple[int, int] | None:
+    """Batch sizes that decode in wide mode, from ROOMAMD_WIDE_DECODE: unset
+    or "1" is the measured default, "0" the kill switch (None: batches of
+    9..64 requests go back to the prefill layer, one eager step per host
+    sync), "LO-HI" an explicit range within 9..64 (the A/B lever)."""
+    v = environ.get("ROOMAMD_WIDE_DECODE", "1").strip()
+    if v == "0":
+        return None
+    if v in ("", "1"):
+        return WIDE_DECODE_DEFAULT
+    lo, sep, hi = v.partition("-")
+    if not (sep and lo.isdigit() and hi.isdigit()
+            and 9 <= int(lo) <= int(hi) <= WIDE_DECODE_MAX):
+        raise ValueError("ROOMAMD_WIDE_DECODE must be 0, 1 or LO-HI with "
+                         f"9 <= LO <= HI <= {WIDE_DECODE_MAX}, got {v!r}")
+    return int(lo), int(hi)
 
 
 @dataclass
@@ -147,8 +178,14 @@ class _DecodeGraph:
     pushes its token into the lane's penalty ring, so one capture serves any
     mix of requests and a block of K replays runs K full decode steps with
     ZERO host work; the host reads the K×B token history once at the end.
-    Padded lanes use a reserved pad slot whose KV writes land in scrap
-    block 0, and sample greedily with penalties off."""
+    Buckets ≤ 8 are exact; the wide buckets (16/32/64, forwards in the
+    model's wide mode) run padded lanes. A padded lane uses the reserved pad
+    slot at position 0 with token 0, samples greedily with penalties off,
+    and advances with the block like any lane: its KV writes go to the pad
+    slot's own block for positions 0..15 and, past that block, through the
+    slot's zero block-table entries into the reserved scrap block 0. All
+    padded lanes of a step are identical, and no request reads either
+    block."""
 
     KMAX = 32
 
@@ -402,6 +439,12 @@ class LocalEngine:
         self._prefill_graphs: dict[int, _PrefillGraph] = {}
         self._graphs_broken = False
         self._prefill_graphs_broken = False
+        # wide decode (9..64 concurrent requests): model mode and graphs,
+        # one switch, read here once; a failed wide capture or replay turns
+        # off only the wide graphs (the ≤ 8 graphs keep working)
+        self.wide_rows = wide_decode_range()
+        self.model.wide_rows = self.wide_rows
+        self._wide_graphs_broken = False
         self.admitter = SessionAdmitter(self.cache, cfg.max_position)
         self._queue: "queue.Queue[GenRequest]" = queue.Queue()
         self._active: list[GenRequest] = []
@@ -411,7 +454,8 @@ class LocalEngine:
         self.stats = {"decode_steps": 0, "decode_tokens": 0, "prefill_tokens": 0,
                       "decode_time": 0.0, "prefill_time": 0.0,
                       "prefill_prep_time": 0.0, "prefill_enq_time": 0.0,
-                      "graphs_captured": 0, "decode_graph_steps": 0}
+                      "graphs_captured": 0, "decode_graph_steps": 0,
+                      "decode_wide_steps": 0}
         # capture prefill-bucket graphs up front, before any agent/encoder
         # thread can put concurrent work on the device mid-capture (captures
         # are thread_local-mode too, but boot-time capture removes the window
@@ -689,14 +733,18 @@ class LocalEngine:
         # multi-step graph block: K bounded by the smallest remaining budget so
         # every request stops exactly at max_new (admission latency is K steps)
         steps = 1
+        # 9..64 requests: the model's wide mode, graph or eager alike
+        wide = (self.wide_rows is not None
+                and self.wide_rows[0] <= len(reqs) <= self.wide_rows[1])
         graph_ok = (self.graphs_enabled and not self._graphs_broken
-                    and len(reqs) <= 8)
+                    and (len(reqs) <= 8
+                         or (wide and not self._wide_graphs_broken)))
         if graph_ok:
             steps = max(1, min(min(r.max_new_tokens - len(r.out_tokens)
                                    for r in reqs), _DecodeGraph.KMAX))
             for r in reqs:
                 self.cache.ensure_capacity(r.slot, r.pos + steps)
-            bucket = next(b for b in DECODE_BUCKETS if b >= len(reqs))
+            bucket = decode_bucket(len(reqs))
             # context band: 64 attention splits once any sequence's KV span
             # passes 8k (shorter per-WG serial chunk chains); banded graphs
             # keep each capture's grid fixed
@@ -726,14 +774,26 @@ class LocalEngine:
                     self._complete(r, ok=True)
                 self.stats["decode_steps"] += steps
                 self.stats["decode_graph_steps"] += steps
+                if wide:
+                    self.stats["decode_wide_steps"] += steps
                 self.stats["decode_tokens"] += steps * len(reqs)
                 self.stats["decode_time"] += time.time() - t0
                 return
             except Exception as e:
                 import sys
-                print(f"[room_amd] hipGraph decode disabled: {e}",
-                      file=sys.stderr)
-                self._graphs_broken = True
+                if wide:
+                    print(f"[room_amd] hipGraph wide decode disabled: {e}",
+                          file=sys.stderr)
+                    self._wide_graphs_broken = True
+                    # as for prefill: fence the device after an aborted capture
+                    try:
+                        torch.cuda.synchronize(dev)
+                    except Exception:
+                        pass
+                else:
+                    print(f"[room_amd] hipGraph decode disabled: {e}",
+                          file=sys.stderr)
+                    self._graphs_broken = True
 
         # eager fallback: one step
         self.model.attn_splits = 64 if max(positions) >= 16384 else 32
@@ -749,6 +809,8 @@ class LocalEngine:
                                     self.cache.kcaches, self.cache.vcaches)
         self._sample_and_append(reqs, logits, positions)
         self.stats["decode_steps"] += 1
+        if wide:
+            self.stats["decode_wide_steps"] += 1
         self.stats["decode_tokens"] += len(reqs)
         self.stats["decode_time"] += time.time() - t0
 

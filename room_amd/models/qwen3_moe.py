@@ -6,7 +6,8 @@ bf16 tensors resident in HBM3E, and the hot ops are the CDNA4 HIP kernels in
 room_amd/ops (RMSNorm, fused QK-norm+RoPE+KV-scatter, split-KV paged
 attention, MFMA flash prefill, H-split router + top-k, MoE pair GEMV /
 grouped MFMA GEMM, BN-specialized dense GEMV, two-stage sampling). At decode
-every projection (QKV/O/router/lm_head) runs on the hand-written GEMVs;
+every projection (QKV/O/router/lm_head) runs on the hand-written GEMVs; wide
+decode (9-64 rows) runs them and the MoE on the skinny MFMA GEMM;
 prefill's large GEMMs go through hipBLASLt via torch.nn.functional.linear.
 
 Inference-only (no autograd); a training path is out of scope for the
@@ -54,6 +55,25 @@ class Qwen3MoEConfig:
                               moe_intermediate_size=256, max_position=4096)
 
 
+WIDE_MAX_ROWS = ops.SKINNY_MAX_ROWS   # tallest wide-decode batch
+
+
+def forward_mode(T: int, has_qtiles: bool,
+                 wide_rows: tuple[int, int] | None = (9, WIDE_MAX_ROWS)) -> str:
+    """Which layer a forward of T rows runs: "decode" (T ≤ 8, GEMV kernels),
+    "wide" (9..64 rows without q-tile descriptors: a decode batch — prefill
+    chunks of that size always carry descriptors) or "prefill". wide_rows
+    narrows the wide range to lo ≤ T ≤ hi (the engine passes the range where
+    wide mode measured faster); None sends every such batch to the prefill
+    layer."""
+    if T <= 8:
+        return "decode"
+    if (wide_rows is not None and not has_qtiles
+            and max(9, wide_rows[0]) <= T <= min(WIDE_MAX_ROWS, wide_rows[1])):
+        return "wide"
+    return "prefill"
+
+
 @dataclass
 class _Step:
     """Per-forward inputs and buffers shared by every layer of one forward()
@@ -71,6 +91,13 @@ class _Step:
     part: torch.Tensor | None = None
     part_ml: torch.Tensor | None = None
     obuf: torch.Tensor | None = None
+    # wide-decode-only (9 ≤ T ≤ 64) buffers, on top of qkv/part/part_ml/obuf
+    attn: torch.Tensor | None = None
+    router_logits: torch.Tensor | None = None
+    gateup: torch.Tensor | None = None      # [T*K, 2I]
+    hmid: torch.Tensor | None = None        # [T*K, I]
+    z: torch.Tensor | None = None           # [T*K, H]
+    moe_out: torch.Tensor | None = None     # [T, H]
 
 
 class Qwen3MoELayer:
@@ -121,6 +148,11 @@ class Qwen3MoEModel:
         self.capture_gemm = False
         self._dense_desc: dict = {}   # T -> (desc, pair_token) for E=1 GEMMs
         self._dense_wpad: dict = {}   # id(w) -> N-padded weight (N % 64 != 0)
+        # wide decode: batch sizes that run _wide_layer. The engine narrows
+        # this to its measured range, or clears it (None) for its kill
+        # switch, which restores the prefill layer for those batches
+        self.wide_rows: tuple[int, int] | None = (9, WIDE_MAX_ROWS)
+        self._wide_rpad: dict = {}    # id(router_w) -> 16-row-padded weight
         cos_t, sin_t = rope_tables(cfg.max_position, cfg.head_dim, cfg.rope_theta)
         self.cos_t = cos_t.to(self.device)
         self.sin_t = sin_t.to(self.device)
@@ -172,7 +204,11 @@ class Qwen3MoEModel:
         # decode-mode (T ≤ 8): dense projections use the hand-written GEMV
         # (hipBLASLt ~1.1 TB/s on M≤8 skinny shapes) and attention uses the
         # split-KV flash-decode kernels so the tiny grid still fills the chip.
-        decode = T <= 8
+        # wide mode (9..64 rows, no q-tiles): the same attention, every GEMM
+        # on the skinny MFMA kernel (_wide_layer).
+        mode = forward_mode(T, qtile_desc is not None, self.wide_rows)
+        decode = mode == "decode"
+        wide = mode == "wide"
         qdim = cfg.num_q_heads * cfg.head_dim
         kvdim = cfg.num_kv_heads * cfg.head_dim
         x = self.embed[tokens.long()]              # [T, H] bf16 (residual stream)
@@ -187,11 +223,13 @@ class Qwen3MoEModel:
         st.pair_token = torch.arange(
             T, device=dev, dtype=torch.int32).repeat_interleave(K)
         st.pair_row = torch.arange(T * K, device=dev, dtype=torch.int32)
-        if decode:
+        if decode or wide:
             st.qkv = torch.empty(T, qdim + 2 * kvdim, dtype=torch.bfloat16,
                                  device=dev)
-            x_alt = torch.empty_like(x)     # residual ping-pong for fused norms
-            st.empty_delta = torch.empty(0, dtype=torch.float32, device=dev)
+            if decode:
+                x_alt = torch.empty_like(x)  # residual ping-pong for fused norms
+                st.empty_delta = torch.empty(0, dtype=torch.float32,
+                                             device=dev)
             nsp = ops.attn_nsplits()
             st.part = torch.empty(T, cfg.num_q_heads, nsp, cfg.head_dim,
                                   dtype=torch.float32, device=dev)
@@ -199,11 +237,25 @@ class Qwen3MoEModel:
                                      dtype=torch.float32, device=dev)
             st.obuf = torch.empty(T, cfg.hidden_size, dtype=torch.bfloat16,
                                   device=dev)
+        if wide:
+            bf = dict(dtype=torch.bfloat16, device=dev)
+            I, P = cfg.moe_intermediate_size, T * K
+            st.attn = torch.empty(T, cfg.num_q_heads, cfg.head_dim, **bf)
+            st.router_logits = torch.empty(
+                T, (cfg.num_experts + 15) // 16 * 16, dtype=torch.float32,
+                device=dev)
+            st.gateup = torch.empty(P, 2 * I, **bf)
+            st.hmid = torch.empty(P, I, **bf)
+            st.z = torch.empty(P, cfg.hidden_size, **bf)
+            st.moe_out = torch.empty(T, cfg.hidden_size, **bf)
 
         for li, layer in enumerate(self.layers):
             if decode:
                 x, x_alt, moe_out = self._decode_layer(
                     layer, kcaches[li], vcaches[li], st, x, x_alt, moe_out)
+            elif wide:
+                moe_out = self._wide_layer(
+                    layer, kcaches[li], vcaches[li], st, x, moe_out)
             else:
                 moe_out = self._prefill_layer(
                     layer, kcaches[li], vcaches[li], st, x, moe_out)
@@ -222,6 +274,12 @@ class Qwen3MoEModel:
             logits = torch.empty(sel.size(0), cfg.vocab_size,
                                  dtype=torch.float32, device=x.device)
             ops.gemv(logits, sel.contiguous(), self.lm_head)
+        elif wide:
+            # f32 logits straight from the MFMA accumulators: no hipBLASLt
+            # (capture-safe) and no bf16 rounding before the sampler
+            logits = torch.empty(sel.size(0), cfg.vocab_size,
+                                 dtype=torch.float32, device=x.device)
+            ops.skinny_gemm(logits, sel.contiguous(), self.lm_head)
         else:
             logits = F.linear(sel, self.lm_head).float()
         return logits
@@ -276,6 +334,77 @@ class Qwen3MoEModel:
         topk_ids, topk_w = ops.router_gemv_topk(hbuf, layer.router_w,
                                                 cfg.num_experts_per_tok)
         return x, x_alt, self._moe(hbuf, layer, topk_ids, topk_w, st)
+
+    def _wide_layer(self, layer: Qwen3MoELayer, kcache: torch.Tensor,
+                    vcache: torch.Tensor, st: "_Step", x: torch.Tensor,
+                    moe_out: torch.Tensor | None) -> torch.Tensor:
+        """One layer at 9 ≤ T ≤ 64 (a decode batch): every projection and
+        both MoE GEMMs on the skinny MFMA GEMM, split-KV attention per row,
+        expert-sorted MoE with the gather combine. No hipBLASLt (capture-
+        safe) and no float atomics (run-to-run deterministic). x is updated
+        in place; returns moe_out."""
+        cfg = self.cfg
+        T = x.size(0)
+        qdim = cfg.num_q_heads * cfg.head_dim
+        hbuf, qkv = st.hbuf, st.qkv
+        # --- attention block
+        if moe_out is None:
+            ops.rmsnorm(hbuf, x, layer.input_norm_w, cfg.rms_eps)
+        else:
+            ops.fused_add_rmsnorm(hbuf, x, moe_out, layer.input_norm_w,
+                                  cfg.rms_eps)
+        ops.skinny_gemm(qkv, hbuf, layer.wqkv)
+        q = qkv[:, :qdim].view(T, cfg.num_q_heads, cfg.head_dim)
+        ops.qk_rope_write_kv(qkv, cfg.num_q_heads, kcache, vcache,
+                             layer.q_norm_w, layer.k_norm_w, self.cos_t,
+                             self.sin_t, st.block_table, st.seq_ids, st.q_pos,
+                             cfg.rms_eps)
+        ops.paged_attention_split(st.attn, q, kcache, vcache, st.block_table,
+                                  st.seq_ids, st.q_pos, st.part, st.part_ml,
+                                  self.scale, splits=self.attn_splits)
+        ops.skinny_gemm(st.obuf, st.attn.view(T, qdim), layer.wo)
+        # --- MoE block
+        ops.fused_add_rmsnorm(hbuf, x, st.obuf, layer.post_attn_norm_w,
+                              cfg.rms_eps)
+        E = cfg.num_experts
+        wr = layer.router_w
+        if E % 16:   # reduced test configs: pad the router to a full fragment
+            wr = self._wide_rpad.get(id(layer.router_w))
+            if wr is None:
+                wr = torch.zeros(st.router_logits.size(1), cfg.hidden_size,
+                                 dtype=torch.bfloat16, device=x.device)
+                wr[:E] = layer.router_w
+                self._wide_rpad[id(layer.router_w)] = wr
+        ops.skinny_gemm(st.router_logits, hbuf, wr)
+        logits = (st.router_logits if E % 16 == 0
+                  else st.router_logits[:, :E].contiguous())
+        topk_ids, topk_w = ops.moe_router(logits, cfg.num_experts_per_tok)
+        return self._moe_wide(hbuf, layer, topk_ids, topk_w, st)
+
+    def _moe_wide(self, hbuf: torch.Tensor, layer: Qwen3MoELayer,
+                  topk_ids: torch.Tensor, topk_w: torch.Tensor,
+                  st: "_Step") -> torch.Tensor:
+        """_moe's expert-sorted path on 16-row tiles: at ≤ 64 tokens an
+        expert sees a handful of rows, so the skinny GEMM streams each
+        touched expert's panel once instead of filling a 128-row tile."""
+        cfg = self.cfg
+        flat_expert = topk_ids.flatten()
+        order = torch.argsort(flat_expert)
+        pair_expert = flat_expert[order].int().contiguous()
+        pair_token = st.pair_token[order].contiguous()
+        P = pair_token.numel()
+        inv_order = torch.empty_like(order)
+        inv_order[order] = torch.arange(P, device=hbuf.device)
+        inv_order = inv_order.int().contiguous()
+        desc = ops.moe_build_desc_device(pair_expert, cfg.num_experts, bm=16)
+        ops.moe_grouped_gemm_skinny(st.gateup, hbuf, layer.w13, pair_token,
+                                    desc)
+        ops.silu_mul(st.hmid, st.gateup)
+        # the down GEMM reads h rows per sorted pair: identity pair map
+        ops.moe_grouped_gemm_skinny(st.z, st.hmid, layer.w2, st.pair_row, desc)
+        ops.moe_combine_gather(st.moe_out, st.z, topk_w.contiguous(),
+                               inv_order)
+        return st.moe_out
 
     def _prefill_layer(self, layer: Qwen3MoELayer, kcache: torch.Tensor,
                        vcache: torch.Tensor, st: "_Step", x: torch.Tensor,

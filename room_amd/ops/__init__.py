@@ -193,12 +193,44 @@ def moe_grouped_gemm128(out: torch.Tensor, x: torch.Tensor, w: torch.Tensor,
     return out
 
 
+def skinny_gemm(y: torch.Tensor, x: torch.Tensor, w: torch.Tensor
+                ) -> torch.Tensor:
+    """y[M,N] = x[M,K] @ w[N,K]^T for 1 <= M <= 64 (wide-decode projections):
+    one MFMA tile of 16/32/48/64 rows chosen from M, weights streamed straight
+    into registers. y is bf16 or f32. A row's result does not depend on M or
+    on the other rows."""
+    if x.size(0) > SKINNY_MAX_ROWS:
+        raise ValueError(f"skinny_gemm handles at most {SKINNY_MAX_ROWS} rows, "
+                         f"got {x.size(0)}")
+    _require().skinny_gemm(y, x, w)
+    return y
+
+
+def moe_grouped_gemm_skinny(out: torch.Tensor, x: torch.Tensor,
+                            w: torch.Tensor, pair_token: torch.Tensor,
+                            tile_desc: torch.Tensor) -> torch.Tensor:
+    """Grouped MFMA GEMM over 16-row m-tiles (tile_desc from
+    moe_build_desc_device(..., bm=16)): out[p] = x[pair_token[p]] @ w[e]^T."""
+    _require().moe_grouped_gemm_skinny(out, x, w, pair_token, tile_desc)
+    return out
+
+
+SKINNY_MAX_ROWS = 64   # tallest skinny_gemm tile (4 MFMA row fragments)
+
+
+def moe_desc_gmax(num_pairs: int, num_experts: int, bm: int = 128) -> int:
+    """Descriptor rows that always suffice: every expert can end in one
+    ragged tile on top of the ceil(P/bm) full ones."""
+    return num_experts + (num_pairs + bm - 1) // bm
+
+
 def moe_build_desc_device(pair_expert_sorted: torch.Tensor,
-                          num_experts: int) -> torch.Tensor:
-    """Sync-free [GMAX,3] (expert,row0,msize) descriptors of 128-row m-tiles;
-    GMAX computed from the host-known pair count, empty tiles zero-sized."""
+                          num_experts: int, bm: int = 128) -> torch.Tensor:
+    """Sync-free [GMAX,3] (expert,row0,msize) descriptors of bm-row m-tiles
+    (128 for moe_grouped_gemm128, 16 for moe_grouped_gemm_skinny); GMAX
+    computed from the host-known pair count, empty tiles zero-sized."""
     P = pair_expert_sorted.numel()
-    gmax = num_experts + (P + 127) // 128
+    gmax = moe_desc_gmax(P, num_experts, bm)
     # NOT torch.bincount: its nbins probe (.max().item()) host-syncs, which
     # aborts hipGraph capture — scatter_add_ is sync-free
     counts = torch.zeros(num_experts, dtype=torch.int64,
@@ -208,7 +240,7 @@ def moe_build_desc_device(pair_expert_sorted: torch.Tensor,
                                    device=pair_expert_sorted.device))
     desc = torch.empty(gmax, 3, dtype=torch.int32,
                        device=pair_expert_sorted.device)
-    _require().moe_build_desc(desc, counts)
+    _require().moe_build_desc(desc, counts, bm)
     return desc
 
 

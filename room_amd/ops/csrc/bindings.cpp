@@ -32,7 +32,11 @@ void moe_gemv_down(torch::Tensor out, torch::Tensor h, torch::Tensor w2,
                    torch::Tensor pair_expert);
 void moe_grouped_gemm128(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                          torch::Tensor pair_token, torch::Tensor tile_desc);
-void moe_build_desc(torch::Tensor desc, torch::Tensor counts);
+void moe_build_desc(torch::Tensor desc, torch::Tensor counts, int64_t bm);
+void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w);
+void moe_grouped_gemm_skinny(torch::Tensor out, torch::Tensor x,
+                             torch::Tensor w, torch::Tensor pair_token,
+                             torch::Tensor tile_desc);
 void moe_combine_gather(torch::Tensor out, torch::Tensor z, torch::Tensor topk_w,
                         torch::Tensor inv_order);
 void paged_attention_split(torch::Tensor out, torch::Tensor q,
@@ -83,7 +87,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gemv_h", &moe_gemv_h, "MoE gate/up GEMV + silu-mul (decode)");
   m.def("moe_gemv_down", &moe_gemv_down, "MoE down GEMV + weighted scatter-add");
   m.def("moe_grouped_gemm128", &moe_grouped_gemm128, "BM=128 grouped MFMA GEMM");
-  m.def("moe_build_desc", &moe_build_desc, "device-side tile desc builder");
+  m.def("moe_build_desc", &moe_build_desc, "device-side tile desc builder",
+        pybind11::arg("desc"), pybind11::arg("counts"),
+        pybind11::arg("bm") = 128);
+  m.def("skinny_gemm", &skinny_gemm,
+        "dense MFMA GEMM for 1..64 rows (wide decode projections)");
+  m.def("moe_grouped_gemm_skinny", &moe_grouped_gemm_skinny,
+        "BM=16 grouped MFMA GEMM, weights straight to VGPRs (wide decode)");
   m.def("moe_combine_gather", &moe_combine_gather, "atomics-free MoE combine");
   m.def("attn_nsplits", &attn_nsplits, "NSPLITS constant");
   m.def("paged_attention_split", &paged_attention_split,

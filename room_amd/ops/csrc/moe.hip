@@ -616,13 +616,14 @@ __global__ void moe_build_desc_kernel(int* __restrict__ desc,      // [GMAX, 3]
   for (; g < gmax; ++g) desc[g * 3 + 2] = 0;
 }
 
-void moe_build_desc(torch::Tensor desc, torch::Tensor counts) {
+void moe_build_desc(torch::Tensor desc, torch::Tensor counts, int64_t bm) {
   const int E = counts.numel();
   const int gmax = desc.size(0);
   TORCH_CHECK(counts.dtype() == torch::kInt64 && desc.size(1) == 3);
+  TORCH_CHECK(bm >= 1 && bm <= G2_BM, "tile height 1..128");
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(moe_build_desc_kernel, dim3(1), dim3(64), 0, s,
-                     desc.data_ptr<int>(), counts.data_ptr<long>(), E, G2_BM,
+                     desc.data_ptr<int>(), counts.data_ptr<long>(), E, (int)bm,
                      gmax);
   HIP_CHECK_KERNEL();
 }

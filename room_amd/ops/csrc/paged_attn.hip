@@ -1,21 +1,21 @@
 // Paged attention for GQA (Qwen3-30B-A3B: 32 q heads / 4 kv heads / head_dim 128).
 //
-// One unified kernel serves prefill AND decode: every query token attends to
-// the paged KV cache of its sequence up to its own position (causal). Decode
-// is the T == batch case. This keeps the agent-swarm engine simple: sessions
-// are KV-cache residency (SURVEY §5 "session-as-KV-cache") and both phases
-// read the same cache.
+// Every query token attends to the paged KV cache of its sequence up to its
+// own position (causal). Sessions are KV-cache residency (SURVEY §5
+// "session-as-KV-cache"), so every phase reads the same cache.
 //
-// Layouts (chosen for this kernel, we own the cache):
+// Layouts (chosen for these kernels, we own the cache):
 //   K,V cache: [num_blocks, kv_heads, BLOCK_SIZE, head_dim] bf16
 //   block_table: [num_seqs, max_blocks] int32
 //
-// Workgroup = (query token, kv head): 256 threads = 4 waves.
-//   score phase: thread (h = t>>5, j = t&31) computes dot(q[h], k[pos_j])
-//                (full 128-dim dot per thread; rows stream through L1)
-//   value phase: thread (h = t>>5, d4 = (t&31)*4) accumulates 4 output dims;
-//                V reads are 32×8B consecutive = coalesced per head-group.
-// Online softmax with per-head running max/sum (flash-style, fp32).
+// Two kernels:
+//   paged_attn_kernel        one workgroup per (query token, kv head), VALU
+//                            dot products, online softmax over 32-position
+//                            chunks. Serves any T.
+//   paged_attn_split_kernel  decode: the KV range of a (token, kv head) is
+//                            split over grid.z workgroups, scores and P·V run
+//                            on the matrix cores straight from registers, and
+//                            paged_attn_merge_kernel combines the partials.
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
@@ -25,6 +25,12 @@
 #define QH_PER_KV 8       // GQA group width (32/4)
 #define HEAD_DIM 128
 
+// Workgroup = (query token, kv head): 256 threads = 4 waves.
+//   score phase: thread (h = t>>5, j = t&31) computes dot(q[h], k[pos_j])
+//                (full 128-dim dot per thread; rows stream through L1)
+//   value phase: thread (h = t>>5, d4 = (t&31)*4) accumulates 4 output dims;
+//                V reads are 32×8B consecutive = coalesced per head-group.
+// Online softmax with per-head running max/sum (flash-style, fp32).
 __global__ __launch_bounds__(256)
 void paged_attn_kernel(short* __restrict__ out,          // [T, Hq, D]
                        const short* __restrict__ q,      // [T, Hq, D]
@@ -201,17 +207,56 @@ void write_kv(torch::Tensor kcache, torch::Tensor vcache, torch::Tensor k,
 // head); each writes an unnormalized partial (acc, m, l); a merge kernel
 // combines. NSPLITS is static so the decode step stays hipGraph-capturable.
 
-// NSPLITS=64 A/B: wins only at L>=16k (63.6->50.0 us B=1), loses at the
-// bench's 4-6k sessions (8.1->8.3 ms/step) and at B=1 (4.5->5.0): empty-split
-// dispatch + 2x merge traffic. Static 32 keeps the decode graph replayable.
+// grid.z is 32 or 64 and static per captured decode graph. On this kernel 32
+// splits win at every measured context (B=5: 21.8 vs 24.0 us at 8k tokens,
+// 36.8 vs 38.3 us at 16k; profiles/PERF_NOTES.md): 64 splits double the
+// empty-split dispatch and the merge traffic and no longer shorten a serial
+// chunk chain. The engine still selects 64 from 16384 tokens.
 #define NSPLITS 32          // default split count (short contexts)
 #define NSPLITS_MAX 64      // part-buffer layout stride; grid.z may be 32 or 64
 
-// CHUNK kv positions are staged and scored per iteration (24 KB LDS). A
-// 64-position chunk (half the barriers, 41 KB LDS) and a double-buffered
-// staging variant were both measured slower in-bench; see
-// profiles/PERF_NOTES.md.
-__global__ __launch_bounds__(256)
+// A split's span is cut into tiles of TILE = BLOCK_SIZE positions, so a tile
+// is exactly one cache block: 16 K rows and 16 V rows of 256 B, contiguous.
+// The workgroup's 4 waves take the tiles round-robin, two per iteration (wave
+// w: tiles w and w+4, then w+8 and w+12, ...), and each keeps a private
+// running (m, l, acc) for the 8 q heads; there is no LDS and no block barrier
+// in the tile loop. The waves combine once at the end through LDS, in wave
+// order, so the result is the same every launch.
+//
+// Per tile pair and wave (lane l: n = l & 15, g = l >> 4):
+//   loads   all 16 (2 tiles x 4 K + 4 V, 16 B per lane each) are issued
+//           before the first MFMA. Up to 4096 tokens at 32 splits that is the
+//           wave's whole share of the split in flight at once.
+//   scores  S^T[pos][head] = K_tile · Q^T on mfma_f32_16x16x32_bf16. The A
+//           operand comes straight from the cache: lane (n, g) reads 16 B of
+//           row n per k-step, four k-steps cover the 256-B row. Q^T is the B
+//           operand, loaded once per wave; head columns 8..15 are zero.
+//           The accumulator holds S[pos 4g + r][head n] in register r.
+//   softmax per head = per lane column, over both tiles at once: max over the
+//           8 registers and over g (shuffles xor 16, xor 32). The row sum
+//           stays a per-lane partial until the epilogue (the rescale factor
+//           is uniform per column).
+//   P·V     O^T[dim][head] += V^T · P on mfma_f32_16x16x32_bf16, k = the 32
+//           positions of the pair. A sum may run over its terms in any order
+//           as long as both operands agree: k-slot 8g + j is row 4g + j of the
+//           first tile for j < 4 and row 4g + j - 4 of the second for j >= 4.
+//           For the B operand those are exactly the two score accumulators'
+//           registers, so P goes in with no lane movement. For the A operand
+//           lane (n, g) loads 16 B (dims 8n..8n+7) of rows 4g..4g+3 of both
+//           tiles, and MFMA m takes element m of each of the eight, i.e. its
+//           16 output rows are dims 8i + m. The 8x8 transpose is in-lane
+//           (v_perm_b32); V never touches LDS.
+//           acc[m][r] = O[head n][dim 32g + 8r + m].
+// Rows at positions >= hi load a valid row of the same block (clamped row
+// index, so p = 0 never meets uninitialised cache) and score -inf; a pair
+// without a second tile loads its first tile twice and masks the copy.
+#define TILE 16
+#define SPLIT_WAVES 4
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
+// 3 waves per SIMD: 640 workgroups at B = 5 are 2.5 waves per SIMD. The bound
+// also keeps the accumulators in VGPRs, where the rescale can reach them.
+__global__ __launch_bounds__(256, 3)
 void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
                              float* __restrict__ part_ml, // [T, Hq, NSPLITS, 2]
                              const short* __restrict__ q,
@@ -222,12 +267,16 @@ void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
                              const int* __restrict__ q_pos,
                              int n_kvheads, int max_blocks, int q_row_stride,
                              float scale) {
+  static_assert(TILE == BLOCK_SIZE, "a tile is one cache block");
   const int t = blockIdx.x;
   const int hk = blockIdx.y;
   const int split = blockIdx.z;
   const int tid = threadIdx.x;
-  const int h = tid >> 5;
+  const int h = tid >> 5;        // epilogue: q head / 4-dim group
   const int sub = tid & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform
+  const int n = tid & 15;        // tile loop: MFMA column / operand row
+  const int g = (tid & 63) >> 4;
   const int seq = seq_ids[t];
   const int bound = q_pos[t] + 1;
   const int n_qheads = n_kvheads * QH_PER_KV;
@@ -244,121 +293,141 @@ void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
   float* acc_out = part + (((long)t * n_qheads + hq) * NSPLITS_MAX + split) * HEAD_DIM;
 
   if (lo >= hi) {  // empty split still writes a neutral partial
-    if (h < QH_PER_KV) {
-      if (sub == 0) { ml[0] = -INFINITY; ml[1] = 0.f; }
-      *reinterpret_cast<f32x4*>(acc_out + sub * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+    if (sub == 0) { ml[0] = -INFINITY; ml[1] = 0.f; }
+    *reinterpret_cast<f32x4*>(acc_out + sub * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
     return;
   }
 
-  // K/V chunks are staged through LDS cooperatively (fully-coalesced bulk
-  // HBM loads, one read per WG instead of one per q-head); the score and
-  // value phases then run out of LDS. Row pad of 8 bf16 keeps the per-lane
-  // row reads off a single bank (same layout as flash_prefill).
-  #define PA_PAD 8
-  __shared__ float q_s[QH_PER_KV][HEAD_DIM];
-  __shared__ float p_s[QH_PER_KV][CHUNK];
-  __shared__ short k_s[CHUNK][HEAD_DIM + PA_PAD];
-  __shared__ short v_s[CHUNK][HEAD_DIM + PA_PAD];
-  for (int i = tid; i < QH_PER_KV * HEAD_DIM; i += blockDim.x) {
-    int hh = i / HEAD_DIM, dd = i % HEAD_DIM;
-    q_s[hh][dd] = bf2f(q[(long)t * q_row_stride
-                         + (hk * QH_PER_KV + hh) * HEAD_DIM + dd]);
+  __shared__ float o_s[SPLIT_WAVES][QH_PER_KV][HEAD_DIM];
+  __shared__ float ml_s[SPLIT_WAVES][QH_PER_KV][2];
+
+  // Q^T B-fragments: element j of k-step ks = q[head n][32 ks + 8 g + j]
+  bf16x8 qf[HEAD_DIM / 32];
+  {
+    const short* qrow = q + (long)t * q_row_stride
+                        + (hk * QH_PER_KV + (n & (QH_PER_KV - 1))) * HEAD_DIM + g * 8;
+    #pragma unroll
+    for (int ks = 0; ks < HEAD_DIM / 32; ++ks) {
+      qf[ks] = *reinterpret_cast<const bf16x8*>(qrow + ks * 32);
+      if (n >= QH_PER_KV) qf[ks] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
   }
 
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[HEAD_DIM / TILE];
+  #pragma unroll
+  for (int m = 0; m < HEAD_DIM / TILE; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m_run = -INFINITY, l_run = 0.f;
+
   const long kv_stride_block = (long)n_kvheads * BLOCK_SIZE * HEAD_DIM;
   const int* btab = block_table + (long)seq * max_blocks;
+  const int tile_end = (hi + TILE - 1) / TILE;   // lo is a multiple of TILE
 
-  // per-thread staging registers (CHUNK/16 vec8 pairs)
-  bf16x8 kreg[CHUNK / 16], vreg[CHUNK / 16];
-  auto issue_loads = [&](int base) {
+  auto issue_loads = [&](bf16x8 (&kr)[4], u32x4 (&vr)[4], int tile) {
+    const int blk = btab[tile];
+    const int last = min(hi - tile * TILE, TILE) - 1;   // last valid row
+    const long boff = (long)blk * kv_stride_block + (long)hk * BLOCK_SIZE * HEAD_DIM;
+    // wave-uniform block base + 32-bit lane byte offset
+    const char* kblk = reinterpret_cast<const char*>(kcache + boff);
+    const char* vblk = reinterpret_cast<const char*>(vcache + boff);
+    const unsigned koff = (min(n, last) * HEAD_DIM + g * 8) * 2;
     #pragma unroll
-    for (int it = 0; it < CHUNK / 16; ++it) {
-      const int idx = tid + it * 256;
-      const int pos_l = (idx * 8) / HEAD_DIM;
-      const int d8 = (idx * 8) % HEAD_DIM;
-      const int pos = base + pos_l;
-      kreg[it] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      vreg[it] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (pos < hi) {
-        const int blk = btab[pos / BLOCK_SIZE];
-        const long off = (long)blk * kv_stride_block
-                         + ((long)hk * BLOCK_SIZE + (pos % BLOCK_SIZE)) * HEAD_DIM + d8;
-        kreg[it] = *reinterpret_cast<const bf16x8*>(kcache + off);
-        vreg[it] = *reinterpret_cast<const bf16x8*>(vcache + off);
-      }
-    }
-  };
-  auto store_regs = [&] {
+    for (int ks = 0; ks < 4; ++ks)
+      kr[ks] = *reinterpret_cast<const bf16x8*>(kblk + koff + ks * 64);
     #pragma unroll
-    for (int it = 0; it < CHUNK / 16; ++it) {
-      const int idx = tid + it * 256;
-      const int pos_l = (idx * 8) / HEAD_DIM;
-      const int d8 = (idx * 8) % HEAD_DIM;
-      *reinterpret_cast<bf16x8*>(&k_s[pos_l][d8]) = kreg[it];
-      *reinterpret_cast<bf16x8*>(&v_s[pos_l][d8]) = vreg[it];
+    for (int j = 0; j < 4; ++j) {
+      const unsigned voff = (min(4 * g + j, last) * HEAD_DIM + n * 8) * 2;
+      vr[j] = *reinterpret_cast<const u32x4*>(vblk + voff);
     }
   };
 
-  // NOTE: the loads are issued once, for the split's first chunk, and every
-  // iteration re-stages those registers (the reload lived only in the removed
-  // double-buffered variant). Splits longer than CHUNK (contexts past
-  // CHUNK * grid.z) therefore score their first chunk repeatedly. Kept as is:
-  // reloading per iteration changes outputs and speed and is its own change.
-  issue_loads(lo);
-  for (int base = lo; base < hi; base += CHUNK) {
-    store_regs();
-    __syncthreads();                 // staged chunk visible to all waves
+  for (int t0 = lo / TILE + wave; t0 < tile_end; t0 += 2 * SPLIT_WAVES) {
+    const bool two = t0 + SPLIT_WAVES < tile_end;
+    const int t1 = two ? t0 + SPLIT_WAVES : t0;
+    bf16x8 k0[4], k1[4];
+    u32x4 v0[4], v1[4];
+    issue_loads(k0, v0, t0);
+    issue_loads(k1, v1, t1);
+    __builtin_amdgcn_sched_barrier(0);   // keep the loads ahead of the MFMAs
 
-    {   // score: thread (h, sub) dots q_s[h] with k_s[sub + r*32]
-      #pragma unroll
-      for (int r = 0; r < CHUNK / 32; ++r) {
-        const int p = sub + r * 32;
-        float s = -INFINITY;
-        if (base + p < hi) {
-          float dot = 0.f;
-          #pragma unroll
-          for (int v8 = 0; v8 < HEAD_DIM / 8; ++v8) {
-            bf16x8 kv = *reinterpret_cast<const bf16x8*>(&k_s[p][v8 * 8]);
-            #pragma unroll
-            for (int j = 0; j < 8; ++j) dot += q_s[h][v8 * 8 + j] * bf2f(kv[j]);
-          }
-          s = dot * scale;
-        }
-        p_s[h][p] = s;
-      }
+    f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0;
+    #pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0[ks], qf[ks], s0, 0, 0, 0);
+      s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1[ks], qf[ks], s1, 0, 0, 0);
     }
-    __syncthreads();
-    {
-      float chunk_max = -INFINITY;
-      #pragma unroll
-      for (int j = 0; j < CHUNK; ++j) chunk_max = fmaxf(chunk_max, p_s[h][j]);
-      const float m_new = fmaxf(m_run, chunk_max);
-      if (m_new != -INFINITY) {
-        const float rescale = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_new);
-        acc[0] *= rescale; acc[1] *= rescale; acc[2] *= rescale; acc[3] *= rescale;
-        l_run *= rescale;
-        const int lim = min(CHUNK, hi - base);
-        for (int j = 0; j < lim; ++j) {
-          const float w = __expf(p_s[h][j] - m_new);
-          l_run += w;
-          bf16x4 vv = *reinterpret_cast<const bf16x4*>(&v_s[j][sub * 4]);
-          acc[0] += w * bf2f(vv[0]);
-          acc[1] += w * bf2f(vv[1]);
-          acc[2] += w * bf2f(vv[2]);
-          acc[3] += w * bf2f(vv[3]);
-        }
-        m_run = m_new;
-      }
+    const int hi1 = two ? hi : 0;        // masks the duplicate tile
+    const int row0 = t0 * TILE + 4 * g, row1 = t1 * TILE + 4 * g;
+    float tmax = -INFINITY;
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      s0[r] = (row0 + r < hi) ? s0[r] * scale : -INFINITY;
+      s1[r] = (row1 + r < hi1) ? s1[r] * scale : -INFINITY;
+      tmax = fmaxf(tmax, fmaxf(s0[r], s1[r]));
     }
-    __syncthreads();  // value reads done before the next store_regs
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, WAVE));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, WAVE));
+    // the first tile's first row is always valid, so m_new is finite
+    const float m_new = fmaxf(m_run, tmax);
+    const float alpha = __expf(m_run - m_new);   // 0 on the wave's first pair
+    bf16x8 pf;
+    float psum = 0.f;
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float p0 = __expf(s0[r] - m_new), p1 = __expf(s1[r] - m_new);
+      psum += p0 + p1;
+      pf[r] = f2bf(p0);
+      pf[4 + r] = f2bf(p1);
+    }
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+    #pragma unroll
+    for (int m = 0; m < HEAD_DIM / TILE; ++m) {
+      // element m of the eight V rows: dword m >> 1, low or high half
+      const uint32_t sel = (m & 1) ? 0x07060302u : 0x05040100u;
+      const int d = m >> 1;
+      const u32x4 vt = u32x4{__builtin_amdgcn_perm(v0[1][d], v0[0][d], sel),
+                             __builtin_amdgcn_perm(v0[3][d], v0[2][d], sel),
+                             __builtin_amdgcn_perm(v1[1][d], v1[0][d], sel),
+                             __builtin_amdgcn_perm(v1[3][d], v1[2][d], sel)};
+      acc[m] *= alpha;
+      acc[m] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          __builtin_bit_cast(bf16x8, vt), pf, acc[m], 0, 0, 0);
+    }
   }
 
-  if (sub == 0) { ml[0] = m_run; ml[1] = l_run; }
-  *reinterpret_cast<f32x4*>(acc_out + sub * 4) =
-      f32x4{acc[0], acc[1], acc[2], acc[3]};
+  // ---- combine the 4 waves' partials in wave order
+  l_run += __shfl_xor(l_run, 16, WAVE);
+  l_run += __shfl_xor(l_run, 32, WAVE);
+  if (n < QH_PER_KV) {
+    #pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float* dst = &o_s[wave][n][32 * g + 8 * r];
+      *reinterpret_cast<f32x4*>(dst) =
+          f32x4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+      *reinterpret_cast<f32x4*>(dst + 4) =
+          f32x4{acc[4][r], acc[5][r], acc[6][r], acc[7][r]};
+    }
+    if (g == 0) { ml_s[wave][n][0] = m_run; ml_s[wave][n][1] = l_run; }
+  }
+  __syncthreads();
+
+  float mw[SPLIT_WAVES], m_star = -INFINITY;
+  #pragma unroll
+  for (int w = 0; w < SPLIT_WAVES; ++w) {
+    mw[w] = ml_s[w][h][0];
+    m_star = fmaxf(m_star, mw[w]);
+  }
+  // a wave without tiles holds (m = -inf, l = 0, zeros): f = 0 adds exactly +0
+  float l_tot = 0.f;
+  f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+  #pragma unroll
+  for (int w = 0; w < SPLIT_WAVES; ++w) {
+    const float f = (mw[w] == -INFINITY) ? 0.f : __expf(mw[w] - m_star);
+    l_tot += ml_s[w][h][1] * f;
+    o += *reinterpret_cast<const f32x4*>(&o_s[w][h][sub * 4]) * f;
+  }
+  if (sub == 0) { ml[0] = m_star; ml[1] = l_tot; }
+  *reinterpret_cast<f32x4*>(acc_out + sub * 4) = o;
 }
 
 // merge: one wave per (t, hq); lane d-pairs combine the NSPLITS partials
@@ -411,6 +480,11 @@ void paged_attention_split(torch::Tensor out, torch::Tensor q,
   TORCH_CHECK(splits == 32 || splits == 64, "splits must be 32 or 64");
   // q may be a strided row-view into the packed qkv buffer
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == q.size(2));
+  // the split kernel loads q, K and V in 16-byte vectors
+  TORCH_CHECK(q.size(2) == HEAD_DIM && q.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "q rows must be 16-byte aligned, head_dim 128");
+  TORCH_CHECK(kcache.size(2) == BLOCK_SIZE);
   const int T = q.size(0);
   const int n_kvheads = kcache.size(1);
   const int n_qheads = n_kvheads * QH_PER_KV;

@@ -67,6 +67,16 @@ def wide_decode_range(environ=os.environ) -> tuple[int, int] | None:
     return int(lo), int(hi)
 
 
+def expert_dtype_from_env(environ=os.environ) -> str:
+    """Expert-weight storage from ROOMAMD_EXPERT_DTYPE: unset or "bf16" is
+    the default, "fp8" the block-scaled e4m3 decode mode."""
+    v = environ.get("ROOMAMD_EXPERT_DTYPE", "").strip() or "bf16"
+    if v not in ("bf16", "fp8"):
+        raise ValueError("ROOMAMD_EXPERT_DTYPE must be bf16 or fp8, "
+                         f"got {v!r}")
+    return v
+
+
 @dataclass
 class GenRequest:
     prompt_tokens: list[int]
@@ -406,8 +416,11 @@ class LocalEngine:
             # see device 0 on every rank of a one-process-per-GPU job and
             # launch kernels on rank-0's streams against rank-k's memory
             self.device = torch.device("cuda", torch.cuda.current_device())
+        # expert-weight storage, read here once (docs/CONFIG.md)
+        self.expert_dtype = expert_dtype_from_env()
         t0 = time.time()
-        self.model = Qwen3MoEModel(cfg, self.device, seed=seed)
+        self.model = Qwen3MoEModel(cfg, self.device, seed=seed,
+                                   expert_dtype=self.expert_dtype)
         self.load_seconds = time.time() - t0
 
         bpb = PagedKVCache.bytes_per_block(cfg.num_layers, cfg.num_kv_heads,

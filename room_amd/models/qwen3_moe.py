@@ -9,6 +9,8 @@ grouped MFMA GEMM, BN-specialized dense GEMV, two-stage sampling). At decode
 every projection (QKV/O/router/lm_head) runs on the hand-written GEMVs; wide
 decode (9-64 rows) runs them and the MoE on the skinny MFMA GEMM;
 prefill's large GEMMs go through hipBLASLt via torch.nn.functional.linear.
+With expert_dtype="fp8" (opt-in) the expert weights are also held as
+block-scaled e4m3 and both decode paths read those (ops/csrc/moe_fp8.hip).
 
 Inference-only (no autograd); a training path is out of scope for the
 reference's semantics (it never trains).
@@ -21,7 +23,10 @@ import torch
 import torch.nn.functional as F
 
 from .. import ops
-from ..ops.reference import rope_tables
+from ..ops.reference import (dequantize_fp8_block, quantize_fp8_block,
+                             rope_tables)
+
+EXPERT_DTYPES = ("bf16", "fp8")
 
 
 @dataclass
@@ -101,7 +106,8 @@ class _Step:
 
 
 class Qwen3MoELayer:
-    def __init__(self, cfg: Qwen3MoEConfig, device: torch.device, gen: torch.Generator):
+    def __init__(self, cfg: Qwen3MoEConfig, device: torch.device,
+                 gen: torch.Generator, expert_dtype: str = "bf16"):
         h, d = cfg.hidden_size, cfg.head_dim
         qdim = cfg.num_q_heads * d
         kvdim = cfg.num_kv_heads * d
@@ -120,21 +126,39 @@ class Qwen3MoELayer:
         self.router_w = rnd(cfg.num_experts, h)
         self.w13 = rnd(cfg.num_experts, 2 * cfg.moe_intermediate_size, h)
         self.w2 = rnd(cfg.num_experts, h, cfg.moe_intermediate_size)
+        if expert_dtype == "fp8":
+            # block-scaled e4m3 for the decode kernels; w13/w2 become the
+            # bf16 image, which holds exactly the fp8 weights' values (the
+            # quantiser's scales are powers of two), for the prefill GEMM
+            self.w13_q, self.w13_s = quantize_fp8_block(self.w13)
+            self.w13 = dequantize_fp8_block(self.w13_q, self.w13_s).to(
+                torch.bfloat16)
+            self.w2_q, self.w2_s = quantize_fp8_block(self.w2)
+            self.w2 = dequantize_fp8_block(self.w2_q, self.w2_s).to(
+                torch.bfloat16)
 
 
 class Qwen3MoEModel:
     """Flat-tensor model (no nn.Module overhead on the decode path)."""
 
     def __init__(self, cfg: Qwen3MoEConfig, device: str | torch.device = "cuda",
-                 seed: int = 1234):
+                 seed: int = 1234, expert_dtype: str = "bf16"):
+        if expert_dtype not in EXPERT_DTYPES:
+            raise ValueError(f"expert_dtype must be one of {EXPERT_DTYPES}, "
+                             f"got {expert_dtype!r}")
         self.cfg = cfg
+        # "fp8": expert weights also held as e4m3 with a scale per 128x128
+        # block, read by the decode paths (narrow GEMVs, wide skinny GEMM);
+        # prefill reads their exact bf16 image
+        self.expert_dtype = expert_dtype
         self.device = torch.device(device)
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
         h = cfg.hidden_size
         self.embed = torch.empty(cfg.vocab_size, h, dtype=torch.bfloat16,
                                  device=self.device).normal_(0, 0.02, generator=gen)
-        self.layers = [Qwen3MoELayer(cfg, self.device, gen)
+        # one layer at a time: the quantiser's f32 transients stay per-layer
+        self.layers = [Qwen3MoELayer(cfg, self.device, gen, expert_dtype)
                        for _ in range(cfg.num_layers)]
         self.final_norm_w = torch.ones(h, dtype=torch.bfloat16, device=self.device)
         self.lm_head = torch.empty(cfg.vocab_size, h, dtype=torch.bfloat16,
@@ -397,11 +421,19 @@ class Qwen3MoEModel:
         inv_order[order] = torch.arange(P, device=hbuf.device)
         inv_order = inv_order.int().contiguous()
         desc = ops.moe_build_desc_device(pair_expert, cfg.num_experts, bm=16)
-        ops.moe_grouped_gemm_skinny(st.gateup, hbuf, layer.w13, pair_token,
-                                    desc)
-        ops.silu_mul(st.hmid, st.gateup)
-        # the down GEMM reads h rows per sorted pair: identity pair map
-        ops.moe_grouped_gemm_skinny(st.z, st.hmid, layer.w2, st.pair_row, desc)
+        if self.expert_dtype == "fp8":
+            ops.moe_grouped_gemm_skinny_fp8(st.gateup, hbuf, layer.w13_q,
+                                            layer.w13_s, pair_token, desc)
+            ops.silu_mul(st.hmid, st.gateup)
+            ops.moe_grouped_gemm_skinny_fp8(st.z, st.hmid, layer.w2_q,
+                                            layer.w2_s, st.pair_row, desc)
+        else:
+            ops.moe_grouped_gemm_skinny(st.gateup, hbuf, layer.w13,
+                                        pair_token, desc)
+            ops.silu_mul(st.hmid, st.gateup)
+            # the down GEMM reads h rows per sorted pair: identity pair map
+            ops.moe_grouped_gemm_skinny(st.z, st.hmid, layer.w2, st.pair_row,
+                                        desc)
         ops.moe_combine_gather(st.moe_out, st.z, topk_w.contiguous(),
                                inv_order)
         return st.moe_out
@@ -462,6 +494,12 @@ class Qwen3MoEModel:
             pair_w = topk_w.flatten().contiguous()
             P = pair_token.numel()
             h = torch.empty(P, I, dtype=torch.bfloat16, device=hbuf.device)
+            if self.expert_dtype == "fp8":
+                ops.moe_gemv_h_fp8(h, hbuf, layer.w13_q, layer.w13_s,
+                                   pair_token, pair_expert, out_zero=out)
+                ops.moe_gemv_down_fp8(out, h, layer.w2_q, layer.w2_s, pair_w,
+                                      pair_token, pair_expert)
+                return out
             ops.moe_gemv_h(h, hbuf, layer.w13, pair_token, pair_expert,
                            out_zero=out)
             ops.moe_gemv_down(out, h, layer.w2, pair_w, pair_token, pair_expert)

@@ -218,6 +218,45 @@ def moe_grouped_gemm_skinny(out: torch.Tensor, x: torch.Tensor,
 SKINNY_MAX_ROWS = 64   # tallest skinny_gemm tile (4 MFMA row fragments)
 
 
+# ---- fp8 expert weights (expert_dtype="fp8"): e4m3fn bytes in the bf16
+# layouts plus one f32 scale per 128x128 block (reference.quantize_fp8_block).
+# Activations stay bf16, accumulation f32; see csrc/moe_fp8.hip.
+
+def moe_gemv_h_fp8(h: torch.Tensor, x: torch.Tensor, w13_q: torch.Tensor,
+                   w13_s: torch.Tensor, pair_token: torch.Tensor,
+                   pair_expert: torch.Tensor,
+                   out_zero: torch.Tensor | None = None) -> torch.Tensor:
+    """moe_gemv_h on fp8 weights: w13_q [E, 2I, H] float8_e4m3fn, w13_s
+    [E, 2I/128, H/128] f32; H and I multiples of 128."""
+    if out_zero is None:
+        out_zero = torch.empty(0, dtype=torch.float32, device=h.device)
+    _require().moe_gemv_h_fp8(h, x, w13_q, w13_s, pair_token, pair_expert,
+                              out_zero)
+    return h
+
+
+def moe_gemv_down_fp8(out: torch.Tensor, h: torch.Tensor, w2_q: torch.Tensor,
+                      w2_s: torch.Tensor, pair_w: torch.Tensor,
+                      pair_token: torch.Tensor, pair_expert: torch.Tensor
+                      ) -> torch.Tensor:
+    """moe_gemv_down on fp8 weights: w2_q [E, H, I] float8_e4m3fn, w2_s
+    [E, H/128, I/128] f32."""
+    _require().moe_gemv_down_fp8(out, h, w2_q, w2_s, pair_w, pair_token,
+                                 pair_expert)
+    return out
+
+
+def moe_grouped_gemm_skinny_fp8(out: torch.Tensor, x: torch.Tensor,
+                                w_q: torch.Tensor, w_s: torch.Tensor,
+                                pair_token: torch.Tensor,
+                                tile_desc: torch.Tensor) -> torch.Tensor:
+    """moe_grouped_gemm_skinny on fp8 weights: w_q [E, N, K] float8_e4m3fn,
+    w_s [E, N/128, K/128] f32. A row's bits depend on (N, K) only."""
+    _require().moe_grouped_gemm_skinny_fp8(out, x, w_q, w_s, pair_token,
+                                           tile_desc)
+    return out
+
+
 def moe_desc_gmax(num_pairs: int, num_experts: int, bm: int = 128) -> int:
     """Descriptor rows that always suffice: every expert can end in one
     ragged tile on top of the ceil(P/bm) full ones."""

@@ -39,6 +39,16 @@ void moe_grouped_gemm_skinny(torch::Tensor out, torch::Tensor x,
                              torch::Tensor tile_desc);
 void moe_combine_gather(torch::Tensor out, torch::Tensor z, torch::Tensor topk_w,
                         torch::Tensor inv_order);
+void moe_gemv_h_fp8(torch::Tensor h, torch::Tensor x, torch::Tensor w13_q,
+                    torch::Tensor w13_s, torch::Tensor pair_token,
+                    torch::Tensor pair_expert, torch::Tensor out_zero);
+void moe_gemv_down_fp8(torch::Tensor out, torch::Tensor h, torch::Tensor w2_q,
+                       torch::Tensor w2_s, torch::Tensor pair_w,
+                       torch::Tensor pair_token, torch::Tensor pair_expert);
+void moe_grouped_gemm_skinny_fp8(torch::Tensor out, torch::Tensor x,
+                                 torch::Tensor w_q, torch::Tensor w_s,
+                                 torch::Tensor pair_token,
+                                 torch::Tensor tile_desc);
 void paged_attention_split(torch::Tensor out, torch::Tensor q,
                            torch::Tensor kcache, torch::Tensor vcache,
                            torch::Tensor block_table, torch::Tensor seq_ids,
@@ -95,6 +105,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_grouped_gemm_skinny", &moe_grouped_gemm_skinny,
         "BM=16 grouped MFMA GEMM, weights straight to VGPRs (wide decode)");
   m.def("moe_combine_gather", &moe_combine_gather, "atomics-free MoE combine");
+  m.def("moe_gemv_h_fp8", &moe_gemv_h_fp8,
+        "MoE gate/up GEMV + silu-mul, block-scaled e4m3 weights (decode)");
+  m.def("moe_gemv_down_fp8", &moe_gemv_down_fp8,
+        "MoE down GEMV + weighted scatter-add, block-scaled e4m3 weights");
+  m.def("moe_grouped_gemm_skinny_fp8", &moe_grouped_gemm_skinny_fp8,
+        "BM=16 grouped MFMA GEMM, block-scaled e4m3 weights (wide decode)");
   m.def("attn_nsplits", &attn_nsplits, "NSPLITS constant");
   m.def("paged_attention_split", &paged_attention_split,
         "split-KV flash-decode paged attention");

@@ -104,6 +104,44 @@ def moe_ref(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
     return out
 
 
+FP8_BLOCK = 128      # scale block edge of the fp8 expert-weight format
+FP8_E4M3_MAX = 448.0
+
+
+def quantize_fp8_block(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Block-scaled e4m3 quantiser of the fp8 expert-weight mode. w: bf16 or
+    f32 [..., N, K] with N and K multiples of 128. Returns (q, scale): q
+    float8_e4m3fn of w's shape, scale f32 [..., N/128, K/128] with
+    w ≈ q · scale per 128×128 block. A block's scale is the power of two
+    2^ceil(log2(amax/448)) (1.0 for an all-zero block), so |w/scale| ≤ 448,
+    the cast never overflows, and every dequantised value is exactly
+    representable in bf16. Plain torch; runs on CPU and GPU."""
+    if w.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"quantize_fp8_block takes bf16 or f32, got {w.dtype}")
+    if w.dim() < 2 or w.size(-2) % FP8_BLOCK or w.size(-1) % FP8_BLOCK:
+        raise ValueError("quantize_fp8_block needs [..., N, K] with N and K "
+                         f"multiples of {FP8_BLOCK}, got {tuple(w.shape)}")
+    B = FP8_BLOCK
+    lead, N, K = w.shape[:-2], w.size(-2), w.size(-1)
+    wb = w.float().reshape(*lead, N // B, B, K // B, B)
+    amax = wb.abs().amax(dim=(-3, -1))                    # [..., N/B, K/B]
+    # frexp: amax/448 = m · 2^e with m in [0.5, 1), so ceil(log2) is e, or
+    # e − 1 at an exact power of two (m = 0.5); no log rounding involved
+    m, e = torch.frexp(amax / FP8_E4M3_MAX)
+    e = torch.where(m == 0.5, e - 1, e)
+    scale = torch.where(amax > 0, torch.ldexp(torch.ones_like(amax), e),
+                        torch.ones_like(amax))
+    q = (wb / scale[..., :, None, :, None]).reshape(w.shape)
+    return q.to(torch.float8_e4m3fn), scale
+
+
+def dequantize_fp8_block(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """f32 q.float() · scale with each scale expanded over its 128×128 block."""
+    B = FP8_BLOCK
+    s = scale.repeat_interleave(B, dim=-2).repeat_interleave(B, dim=-1)
+    return q.float() * s
+
+
 def vs_topk_ref(mat: torch.Tensor, query: torch.Tensor, k: int
                 ) -> tuple[torch.Tensor, torch.Tensor]:
     scores = mat.float() @ query.float()

@@ -20,6 +20,7 @@ SOURCES = [
     "room_amd/ops/csrc/norm_rope.hip",
     "room_amd/ops/csrc/paged_attn.hip",
     "room_amd/ops/csrc/moe.hip",
+    "room_amd/ops/csrc/moe_fp8.hip",
     "room_amd/ops/csrc/gemv.hip",
     "room_amd/ops/csrc/skinny_gemm.hip",
     "room_amd/ops/csrc/flash_prefill.hip",

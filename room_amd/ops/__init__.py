@@ -8,6 +8,8 @@ from __future__ import annotations
 
 import torch
 
+from ..engine.step_plan import qtile_list
+
 _C = None
 _import_error: Exception | None = None
 try:
@@ -120,19 +122,17 @@ def flash_prefill(out: torch.Tensor, q: torch.Tensor, kcache: torch.Tensor,
     return out
 
 
+def flash_prefill_qtile() -> int:
+    """Q rows per flash_prefill tile (FP_QTOK, compiled into the kernel)."""
+    if _C is not None and hasattr(_C, "flash_prefill_qtile"):
+        return int(_C.flash_prefill_qtile())
+    return 32
+
+
 def build_qtile_desc(segments: list, device) -> torch.Tensor:
     """Q-tile descriptors from host-known prefill segments [(row0, count), ...]
-    (one sequence per segment) — no device sync. Tile rows match the
-    flash_prefill kernel's FP_QTOK."""
-    qt = int(_C.flash_prefill_qtile()) if (
-        _C is not None and hasattr(_C, "flash_prefill_qtile")) else 32
-    desc = []
-    for row0, count in segments:
-        r = row0
-        while r < row0 + count:
-            n = min(qt, row0 + count - r)
-            desc.append((r, n))
-            r += n
+    (one sequence per segment) — no device sync."""
+    desc = qtile_list(segments, flash_prefill_qtile())
     if not desc:
         return torch.zeros(0, 2, dtype=torch.int32, device=device)
     return torch.tensor(desc, dtype=torch.int32, device=device)

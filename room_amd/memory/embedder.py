@@ -56,7 +56,7 @@ def embed(text: str) -> list[float]:
     forward costs ~40 ms of event-loop time per call — cache hits remove
     the prompt-build stagger that delays agents joining the decode batch."""
     mode = _mode()
-    key = (mode, text)
+    key = (_cache_tag(mode), text)
     hit = _EMBED_CACHE.get(key)
     if hit is not None:
         return list(hit)
@@ -65,10 +65,51 @@ def embed(text: str) -> list[float]:
         vec = encoder.encode_texts([text])[0]
     else:
         vec = embed_hash(text)
-    if len(_EMBED_CACHE) >= _EMBED_CACHE_MAX:
-        _EMBED_CACHE.pop(next(iter(_EMBED_CACHE)))
-    _EMBED_CACHE[key] = tuple(vec)
+    _cache_put(key, vec)
     return vec
+
+
+def _cache_tag(mode: str) -> str:
+    """Cache namespace: the two encoder implementations agree to bf16
+    precision only, so their vectors are cached apart."""
+    if mode == "encoder":
+        from . import encoder
+        if encoder.default_impl() == "hip":
+            return "encoder:hip"
+    return mode
+
+
+def _cache_put(key: tuple, vec: list[float]) -> None:
+    if len(_EMBED_CACHE) >= _EMBED_CACHE_MAX:
+        _EMBED_CACHE.pop(next(iter(_EMBED_CACHE)), None)
+    _EMBED_CACHE[key] = tuple(vec)
+
+
+def embed_many(texts: list[str]) -> list[list[float]]:
+    """embed() for several texts. With the encoder on its hip implementation
+    (ROOMAMD_ENCODER_IMPL=hip) every cache miss goes to the encoder in one
+    packed forward, whose rows do not depend on the batch, so each result is
+    what embed(text) returns. In every other mode this is the per-text loop."""
+    mode = _mode()
+    tag = _cache_tag(mode)
+    if tag != "encoder:hip":
+        return [embed(t) for t in texts]
+    from . import encoder
+    out: list = [None] * len(texts)
+    misses: dict[str, list[int]] = {}     # distinct missing text → positions
+    for i, t in enumerate(texts):
+        hit = _EMBED_CACHE.get((tag, t))
+        if hit is not None:
+            out[i] = list(hit)
+        else:
+            misses.setdefault(t, []).append(i)
+    if misses:
+        order = list(misses)
+        for t, vec in zip(order, encoder.encode_texts(order)):
+            _cache_put((tag, t), vec)
+            for i in misses[t]:
+                out[i] = list(vec)
+    return out
 
 
 def embed_hash(text: str) -> list[float]:

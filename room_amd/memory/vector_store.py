@@ -280,7 +280,7 @@ class MemoryService:
         from ..db import queries as q
         if len(room_ids) != len(queries):
             raise ValueError("room_ids and queries must have the same length")
-        qvecs = [self.embedder.embed(text) for text in queries]
+        qvecs = self.embedder.embed_many(list(queries))
         semantic = self.store.search_batch(qvecs, k=20, room_ids=list(room_ids))
         with self.ldb as db:
             fused = [q.hybrid_search(db, text, qvec, limit=limit, room_id=rid,
@@ -300,11 +300,14 @@ class MemoryService:
         with self.ldb as db:
             pending = q.get_unembedded_entities(db, limit=batch)
             done = 0
+            texts = []
             for ent in pending:
                 obs = q.get_observations(db, ent["id"])[:5]
-                text = (ent["name"] + " " +
-                        " ".join(o["content"] for o in obs))[:2000]
-                vec = self.embedder.embed(text)
+                texts.append((ent["name"] + " " +
+                              " ".join(o["content"] for o in obs))[:2000])
+            # one encoder call for the batch where the embedder batches
+            vecs = self.embedder.embed_many(texts)
+            for ent, text, vec in zip(pending, texts, vecs):
                 q.upsert_embedding(db, ent["id"], vec,
                                    self.embedder.text_hash(text))
                 try:

@@ -381,3 +381,71 @@ def vs_topk_scoped(mat: torch.Tensor, tags: torch.Tensor, queries: torch.Tensor,
     _require().vs_topk_scoped(out_v, out_i, cand_v, cand_i, mat, tags, queries,
                               scopes, k)
     return out_v, out_i
+
+
+# ---- memory encoder (MiniEncoder impl="hip"); see csrc/encoder.hip. Rows of
+# all texts are packed without padding; cu_rows [B+1] int32 holds cumulative
+# row offsets, every segment 1..ENCODER_MAX_PIECES rows.
+
+ENCODER_DIM = 384
+ENCODER_MAX_PIECES = 128   # ENC_MAXLEN in encoder.hip
+
+
+def _check_cu_rows(op: str, cu_rows: torch.Tensor, rows: int,
+                   cu_rows_host) -> None:
+    """Segment checks run on host values: cu_rows_host (a list or CPU tensor
+    the caller already has; no device sync) or a copy of cu_rows."""
+    if cu_rows.dtype != torch.int32 or cu_rows.dim() != 1 or cu_rows.numel() < 2:
+        raise RuntimeError(f"{op}: cu_rows must be int32 [B+1]")
+    cu = cu_rows_host if cu_rows_host is not None else cu_rows.cpu()
+    cu = [int(v) for v in cu]
+    if len(cu) != cu_rows.numel() or cu[0] != 0:
+        raise RuntimeError(f"{op}: cu_rows must start at 0 and hold B+1 offsets")
+    for lo, hi in zip(cu, cu[1:]):
+        if not 1 <= hi - lo <= ENCODER_MAX_PIECES:
+            raise RuntimeError(
+                f"{op}: segment length {hi - lo} outside "
+                f"1..{ENCODER_MAX_PIECES}")
+    if cu[-1] != rows:
+        raise RuntimeError(f"{op}: cu_rows[-1] = {cu[-1]} but {rows} rows")
+
+
+def encoder_embed(x: torch.Tensor, feats: torch.Tensor, pos_ids: torch.Tensor,
+                  pos_table: torch.Tensor) -> torch.Tensor:
+    """x[r] = Σ of the row's four sparse ±0.5 features + pos_table[pos_ids[r]]
+    as bf16 [R, 384]. feats [R, 4] int32, each (index << 1) | (1 for +0.5, 0
+    for -0.5); features sharing an index accumulate. pos_table f32 [P, 384]."""
+    _require().encoder_embed(x, feats, pos_ids, pos_table)
+    return x
+
+
+def encoder_attention(out: torch.Tensor, qkv: torch.Tensor,
+                      cu_rows: torch.Tensor, cu_rows_host=None) -> torch.Tensor:
+    """Bidirectional softmax attention inside each packed segment. qkv
+    [R, 1152] bf16, rows q|k|v of 12 heads x 32; out [R, 384] bf16; scale
+    32^-0.5 applied inside. A segment's output depends on its own rows only
+    and has the same bits wherever it sits in the pack."""
+    if qkv.dim() != 2 or qkv.size(1) != 3 * ENCODER_DIM:
+        raise RuntimeError("encoder_attention: qkv rows are q|k|v, 1152 wide")
+    _check_cu_rows("encoder_attention", cu_rows, qkv.size(0), cu_rows_host)
+    _require().encoder_attention(out, qkv, cu_rows)
+    return out
+
+
+def gelu_(u: torch.Tensor) -> torch.Tensor:
+    """Exact (erf) GELU in place on a contiguous bf16 tensor."""
+    _require().gelu_(u)
+    return u
+
+
+def encoder_pool(out: torch.Tensor, h: torch.Tensor, cu_rows: torch.Tensor,
+                 mu: torch.Tensor, cu_rows_host=None,
+                 normalize: bool = True) -> torch.Tensor:
+    """out[b] = L2-normalised (mean of segment b's rows of h - mu), f32
+    [B, 384]; rows summed first to last. normalize=False writes the centred
+    mean itself."""
+    if h.dim() != 2 or h.size(1) != ENCODER_DIM:
+        raise RuntimeError("encoder_pool: h must be [R, 384]")
+    _check_cu_rows("encoder_pool", cu_rows, h.size(0), cu_rows_host)
+    _require().encoder_pool(out, h, cu_rows, mu, normalize)
+    return out

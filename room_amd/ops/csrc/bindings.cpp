@@ -81,6 +81,13 @@ void vs_topk_scoped(torch::Tensor out_v, torch::Tensor out_i,
                     torch::Tensor cand_v, torch::Tensor cand_i,
                     torch::Tensor mat, torch::Tensor tags,
                     torch::Tensor queries, torch::Tensor scopes, int64_t K);
+void encoder_embed(torch::Tensor x, torch::Tensor feats, torch::Tensor pos_ids,
+                   torch::Tensor pos_table);
+void encoder_attention(torch::Tensor out, torch::Tensor qkv,
+                       torch::Tensor cu_rows);
+void gelu_(torch::Tensor u);
+void encoder_pool(torch::Tensor out, torch::Tensor h, torch::Tensor cu_rows,
+                  torch::Tensor mu, bool normalize);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm", &rmsnorm, "RMSNorm (bf16, CDNA4)");
@@ -125,4 +132,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vs_topk", &vs_topk, "vector-store cosine top-k over bf16 matrix");
   m.def("vs_topk_scoped", &vs_topk_scoped,
         "room-scoped cosine top-k for a batch of up to 8 queries");
+  m.def("encoder_embed", &encoder_embed,
+        "memory encoder input rows: hash features + position row");
+  m.def("encoder_attention", &encoder_attention,
+        "bidirectional MFMA attention over packed segments (head dim 32)");
+  m.def("gelu_", &gelu_, "exact (erf) GELU in place (bf16)");
+  m.def("encoder_pool", &encoder_pool,
+        "segment mean, centring and L2 normalisation");
 }

@@ -169,6 +169,49 @@ def vs_topk_scoped_ref(mat: torch.Tensor, tags: torch.Tensor,
     return v, i
 
 
+# ---- memory encoder (csrc/encoder.hip): fp32 math on the given values
+
+def encoder_embed_ref(feats: torch.Tensor, pos_ids: torch.Tensor,
+                      pos_table: torch.Tensor) -> torch.Tensor:
+    """feats [R, 4] int32 of (index << 1) | plus; collisions accumulate. The
+    ±0.5 sums are exact, so the result is one f32 add and one rounding."""
+    R = feats.size(0)
+    v = torch.zeros(R, pos_table.size(1), dtype=torch.float32,
+                    device=feats.device)
+    idx = (feats >> 1).long()
+    sign = (feats & 1).float() - 0.5
+    v.scatter_add_(1, idx, sign)
+    return (v + pos_table.float()[pos_ids.long()]).to(torch.bfloat16)
+
+
+def encoder_attention_ref(qkv: torch.Tensor, cu_rows: list[int],
+                          heads: int = 12) -> torch.Tensor:
+    """Bidirectional softmax attention per packed segment, fp32, on rows of
+    q|k|v; returns fp32 [R, D]."""
+    R, D = qkv.size(0), qkv.size(1) // 3
+    hd = D // heads
+    out = torch.empty(R, D, dtype=torch.float32, device=qkv.device)
+    for lo, hi in zip(cu_rows, cu_rows[1:]):
+        seg = qkv[lo:hi].float().view(hi - lo, 3, heads, hd)
+        q, k, v = (seg[:, i].transpose(0, 1) for i in range(3))   # [H, T, hd]
+        s = (q @ k.transpose(-1, -2)) * hd ** -0.5
+        out[lo:hi] = (torch.softmax(s, dim=-1) @ v).transpose(0, 1).reshape(
+            hi - lo, D)
+    return out
+
+
+def gelu_ref(u: torch.Tensor) -> torch.Tensor:
+    return F.gelu(u.float()).to(torch.bfloat16)
+
+
+def encoder_pool_ref(h: torch.Tensor, cu_rows: list[int], mu: torch.Tensor,
+                     normalize: bool = True) -> torch.Tensor:
+    rows = [h[lo:hi].float().mean(0) - mu.float()
+            for lo, hi in zip(cu_rows, cu_rows[1:])]
+    out = torch.stack(rows)
+    return F.normalize(out, dim=-1) if normalize else out
+
+
 RING = 256   # token-history ring entries per row
 
 

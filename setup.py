@@ -26,6 +26,7 @@ SOURCES = [
     "room_amd/ops/csrc/flash_prefill.hip",
     "room_amd/ops/csrc/sampling.hip",
     "room_amd/ops/csrc/vector_store.hip",
+    "room_amd/ops/csrc/encoder.hip",
 ]
 
 setup(

@@ -90,13 +90,13 @@ class _Step:
     hbuf: torch.Tensor                      # normed activations [T, H]
     pair_token: torch.Tensor | None = None  # MoE pair -> token row [T*K]
     pair_row: torch.Tensor | None = None    # identity pair map [T*K]
-    # decode-only (T ≤ 8) buffers
+    # decode (T ≤ 8) buffers; empty_delta is decode-only
     qkv: torch.Tensor | None = None
     empty_delta: torch.Tensor | None = None
     part: torch.Tensor | None = None
     part_ml: torch.Tensor | None = None
-    obuf: torch.Tensor | None = None
-    # wide-decode-only (9 ≤ T ≤ 64) buffers, on top of qkv/part/part_ml/obuf
+    # wide-decode-only (9 ≤ T ≤ 64) buffers, on top of qkv/part/part_ml
+    obuf: torch.Tensor | None = None        # O projection output [T, H]
     attn: torch.Tensor | None = None
     router_logits: torch.Tensor | None = None
     gateup: torch.Tensor | None = None      # [T*K, 2I]
@@ -259,10 +259,9 @@ class Qwen3MoEModel:
                                   dtype=torch.float32, device=dev)
             st.part_ml = torch.empty(T, cfg.num_q_heads, nsp, 2,
                                      dtype=torch.float32, device=dev)
-            st.obuf = torch.empty(T, cfg.hidden_size, dtype=torch.bfloat16,
-                                  device=dev)
         if wide:
             bf = dict(dtype=torch.bfloat16, device=dev)
+            st.obuf = torch.empty(T, cfg.hidden_size, **bf)
             I, P = cfg.moe_intermediate_size, T * K
             st.attn = torch.empty(T, cfg.num_q_heads, cfg.head_dim, **bf)
             st.router_logits = torch.empty(
@@ -321,10 +320,11 @@ class Qwen3MoEModel:
         # --- attention block
         if T <= 2:
             # fused add(moe_prev)+RMSNorm+QKV-GEMV: one kernel replaces
-            # fused_add_rmsnorm + gemv. Wins at B≤2 where the removed
-            # launch/drain bubble dominates (5.7 → 5.2 ms/step at B=1);
-            # at B≥3 the cooperative norm passes cost more than the bubble
-            # (measured 9.1 vs 8.8 at B=5) so the unfused path is used.
+            # fused_add_rmsnorm (or rmsnorm) + gemv, with their bits; the
+            # residual lands in the other ping-pong buffer. Faster than the
+            # pair at B ≤ 2 (8.6 → 6.7 and 9.4 → 7.8 µs per layer); at B = 5
+            # it ties (11.6 vs 11.8) and at B = 8 it loses (14.2 vs 17.0), so
+            # larger batches keep the two launches
             if moe_out is None:
                 ops.gemv_addnorm(qkv, x, st.empty_delta, x, layer.input_norm_w,
                                  layer.wqkv, cfg.rms_eps)
@@ -351,12 +351,14 @@ class Qwen3MoEModel:
         ops.paged_attention_split(attn, q, kcache, vcache, st.block_table,
                                   st.seq_ids, st.q_pos, st.part, st.part_ml,
                                   self.scale, splits=self.attn_splits)
-        ops.gemv(st.obuf, attn.reshape(T, qdim), layer.wo)
+        # O projection with the residual add in its epilogue (x updated in
+        # place), then the post-attention norm inside the router GEMV, which
+        # also leaves the normed rows in hbuf for the MoE: no norm launch
+        ops.gemv_residual(x, attn.reshape(T, qdim), layer.wo)
         # --- MoE block
-        ops.fused_add_rmsnorm(hbuf, x, st.obuf, layer.post_attn_norm_w,
-                              cfg.rms_eps)
-        topk_ids, topk_w = ops.router_gemv_topk(hbuf, layer.router_w,
-                                                cfg.num_experts_per_tok)
+        topk_ids, topk_w = ops.router_norm_gemv_topk(
+            hbuf, x, layer.post_attn_norm_w, layer.router_w,
+            cfg.num_experts_per_tok, cfg.rms_eps)
         return x, x_alt, self._moe(hbuf, layer, topk_ids, topk_w, st)
 
     def _wide_layer(self, layer: Qwen3MoELayer, kcache: torch.Tensor,

@@ -111,6 +111,15 @@ def gemv(y: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def gemv_residual(r: torch.Tensor, x: torch.Tensor, w: torch.Tensor
+                  ) -> torch.Tensor:
+    """r[B,N] = bf16(bf16(x[B,H] @ w[N,H]^T) + r) in place for B<=8: the
+    decode O projection with the residual add in its epilogue. Same bits in r
+    as gemv (bf16 out) followed by fused_add_rmsnorm's add."""
+    _require().gemv_residual(r, x, w)
+    return r
+
+
 def flash_prefill(out: torch.Tensor, q: torch.Tensor, kcache: torch.Tensor,
                   vcache: torch.Tensor, block_table: torch.Tensor,
                   seq_ids: torch.Tensor, q_pos: torch.Tensor,
@@ -142,7 +151,9 @@ def gemv_addnorm(y: torch.Tensor, x: torch.Tensor, delta: torch.Tensor,
                  x_out: torch.Tensor, gamma: torch.Tensor, w: torch.Tensor,
                  eps: float = 1e-6) -> torch.Tensor:
     """y = rmsnorm(x + delta)·γ @ w^T; x_out = x + delta (pass delta with
-    numel 0 for a plain norm+gemv). Decode-path fusion (B ≤ 8)."""
+    numel 0 for a plain norm+gemv; x_out is then not written). Decode-path
+    fusion (B ≤ 8) with the bits of fused_add_rmsnorm (or rmsnorm) followed by
+    gemv."""
     _require().gemv_addnorm(y, x, delta, x_out, gamma, w, eps)
     return y
 
@@ -163,6 +174,21 @@ def router_gemv_topk(x: torch.Tensor, wr: torch.Tensor,
     ids = torch.empty(T, k, dtype=torch.int32, device=x.device)
     w = torch.empty(T, k, dtype=torch.float32, device=x.device)
     _require().router_gemv_topk(ids, w, x, wr, k)
+    return ids, w
+
+
+def router_norm_gemv_topk(hbuf: torch.Tensor, r: torch.Tensor,
+                          gamma: torch.Tensor, wr: torch.Tensor, k: int,
+                          eps: float = 1e-6
+                          ) -> tuple[torch.Tensor, torch.Tensor]:
+    """Decode router on the residual rows r [T, H]: hbuf = rmsnorm(r)·γ and
+    the top-k of hbuf @ wr^T, with the norm computed inside the router GEMV
+    (one wave per expert row and token). Same bits in hbuf, ids and weights
+    as rmsnorm followed by router_gemv_topk."""
+    T = r.size(0)
+    ids = torch.empty(T, k, dtype=torch.int32, device=r.device)
+    w = torch.empty(T, k, dtype=torch.float32, device=r.device)
+    _require().router_norm_gemv_topk(ids, w, hbuf, r, gamma, wr, k, eps)
     return ids, w
 
 

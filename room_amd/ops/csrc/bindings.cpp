@@ -24,6 +24,10 @@ void moe_router(torch::Tensor topk_ids, torch::Tensor topk_w, torch::Tensor logi
                 int64_t K);
 void router_gemv_topk(torch::Tensor topk_ids, torch::Tensor topk_w,
                       torch::Tensor x, torch::Tensor wr, int64_t K);
+void router_norm_gemv_topk(torch::Tensor topk_ids, torch::Tensor topk_w,
+                           torch::Tensor hbuf, torch::Tensor r,
+                           torch::Tensor gamma, torch::Tensor wr, int64_t K,
+                           double eps);
 void moe_gemv_h(torch::Tensor h, torch::Tensor x, torch::Tensor w13,
                 torch::Tensor pair_token, torch::Tensor pair_expert,
                 torch::Tensor out_zero);
@@ -62,6 +66,7 @@ void flash_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
                    torch::Tensor seq_ids, torch::Tensor q_pos,
                    torch::Tensor tile_desc, double scale);
 void gemv(torch::Tensor y, torch::Tensor x, torch::Tensor w);
+void gemv_residual(torch::Tensor r, torch::Tensor x, torch::Tensor w);
 void gemv_addnorm(torch::Tensor y, torch::Tensor x, torch::Tensor delta,
                   torch::Tensor x_out, torch::Tensor gamma, torch::Tensor w,
                   double eps);
@@ -101,6 +106,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_router", &moe_router, "softmax top-k router");
   m.def("router_gemv_topk", &router_gemv_topk,
         "H-split router GEMV + top-k (two kernels, wide grid)");
+  m.def("router_norm_gemv_topk", &router_norm_gemv_topk,
+        "RMSNorm + H-split router GEMV + top-k; also stores the normed rows");
   m.def("moe_gemv_h", &moe_gemv_h, "MoE gate/up GEMV + silu-mul (decode)");
   m.def("moe_gemv_down", &moe_gemv_down, "MoE down GEMV + weighted scatter-add");
   m.def("moe_grouped_gemm128", &moe_grouped_gemm128, "BM=128 grouped MFMA GEMM");
@@ -124,6 +131,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_prefill", &flash_prefill, "MFMA flash-attention prefill");
   m.def("flash_prefill_qtile", &flash_prefill_qtile, "q-tile rows constant");
   m.def("gemv", &gemv, "dense skinny-batch GEMV (decode projections)");
+  m.def("gemv_residual", &gemv_residual,
+        "r += bf16(x @ w^T) in place (decode O projection + residual add)");
   m.def("gemv_addnorm", &gemv_addnorm,
         "fused residual-add + RMSNorm + GEMV (decode)");
   m.def("sample_rows", &sample_rows,

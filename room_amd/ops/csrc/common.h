@@ -32,6 +32,30 @@ DEV short f2bf(float f) {
   return (short)(c.u32 >> 16);
 }
 
+// acc + Σ f_j² over one 8-vector, j ascending: the per-vector step of every
+// RMSNorm row sum. Kernels that must agree bit for bit on a row's sum of
+// squares (the norm kernels and the fusions that fold a norm into a GEMV) all
+// take it from here. Each square is rounded before its add (no fma
+// contraction), which is what the norm kernels have always compiled to.
+DEV float sumsq8(float acc, bf16x8 v) {
+  #pragma clang fp contract(off)
+  #pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float f = bf2f(v[j]);
+    acc += f * f;
+  }
+  return acc;
+}
+
+// acc + Σ w_j·x_j over one 8-vector, j ascending, each product rounded before
+// its add: the router GEMV's step, shared by its plain and norm-fused kernels.
+DEV float dot8_unfused(float acc, const float (&wf)[8], bf16x8 xv) {
+  #pragma clang fp contract(off)
+  #pragma unroll
+  for (int j = 0; j < 8; ++j) acc += wf[j] * bf2f(xv[j]);
+  return acc;
+}
+
 // full-wave sum reduction (64 lanes)
 DEV float wave_reduce_sum(float v) {
   #pragma unroll

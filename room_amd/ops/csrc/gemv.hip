@@ -9,6 +9,9 @@
 #include "common.h"
 
 #define GEMV_MAXB 8
+// gemv_addnorm's waves per workgroup: 8 measured fastest of 4, 8 and 16 at
+// every B (profiles/PERF_NOTES.md); the kernel takes any of the three
+#define GEMV_ADDNORM_WPB 8
 
 // this lane's 8 elements of each of the BN rows at xs (row stride H)
 template <int BN>
@@ -37,10 +40,23 @@ DEV void gemv_fma8(float (&acc)[BN], bf16x8 wv, const bf16x8 (&xv)[BN]) {
 // is then issued before the first FMA, so the row costs one HBM round trip
 // and not NIT in series; the x loads (L2 or LDS hits) run one iteration ahead
 // of their FMAs. NIT = 0 takes any multiple of 512 and loads inside the loop.
-// The FMA order per accumulator is the same in both.
+// The FMA order per accumulator is the same in both. It comes in two halves,
+// so that a kernel can put work of its own under the W loads.
+
+// first half: the NIT 16-byte W loads of this lane for the row at wrow
+template <int NIT>
+DEV void gemv_load_w(bf16x8 (&wv)[NIT > 0 ? NIT : 1], const short* wrow,
+                     int lane) {
+  #pragma unroll
+  for (int it = 0; it < NIT; ++it)
+    wv[it] = *reinterpret_cast<const bf16x8*>(wrow + lane * 8 + it * WAVE * 8);
+}
+
+// gemv_row_dot's second half: the dots against W vectors already loaded (or
+// in flight) in wv; NIT = 0 ignores wv and loads inside the loop.
 template <int BN, int NIT>
-DEV void gemv_row_dot(float (&acc)[BN], const short* wrow, const short* xs,
-                      int H, int lane) {
+DEV void gemv_row_dot_w(float (&acc)[BN], const bf16x8 (&wv)[NIT > 0 ? NIT : 1],
+                        const short* wrow, const short* xs, int H, int lane) {
   #pragma unroll
   for (int b = 0; b < BN; ++b) acc[b] = 0.f;
   if constexpr (NIT > 0) {
@@ -48,10 +64,7 @@ DEV void gemv_row_dot(float (&acc)[BN], const short* wrow, const short* xs,
     // x loads run PF iterations ahead of their FMAs; 2 measured slower
     // in-bench (more registers, nothing left to hide)
     constexpr int PF = 1;
-    bf16x8 wv[NIT], xv[PF + 1][BN];
-    #pragma unroll
-    for (int it = 0; it < NIT; ++it)
-      wv[it] = *reinterpret_cast<const bf16x8*>(wrow + lane * 8 + it * WAVE * 8);
+    bf16x8 xv[PF + 1][BN];
     #pragma unroll
     for (int it = 0; it < PF && it < NIT; ++it)
       gemv_load_x<BN>(xv[it], xs + lane * 8 + it * WAVE * 8, HC);
@@ -74,6 +87,14 @@ DEV void gemv_row_dot(float (&acc)[BN], const short* wrow, const short* xs,
       gemv_fma8<BN>(acc, *reinterpret_cast<const bf16x8*>(wrow + base), xv);
     }
   }
+}
+
+template <int BN, int NIT>
+DEV void gemv_row_dot(float (&acc)[BN], const short* wrow, const short* xs,
+                      int H, int lane) {
+  bf16x8 wv[NIT > 0 ? NIT : 1];
+  gemv_load_w<NIT>(wv, wrow, lane);
+  gemv_row_dot_w<BN, NIT>(acc, wv, wrow, xs, H, lane);
 }
 
 // The BN wave sums run as one interleaved xor butterfly (same pairing as
@@ -186,154 +207,280 @@ void gemv(torch::Tensor y, torch::Tensor x, torch::Tensor w) {
   HIP_CHECK_KERNEL();
 }
 
-// ------------------------------------------------ fused add+RMSNorm+GEMV
-// y[B,N] = rmsnorm(x + delta)·γ @ W^T, and (block 0 only) x_out = x + delta.
-// Folds the per-layer fused_add_rmsnorm kernel and the normed-activation
-// buffer round-trip into the projection itself: each wave already streams the
-// full activation row, so the row norm is one extra L1-hot pass (decode chains
-// ~14 dependent small kernels/layer; every removed kernel removes a
-// launch+fill/drain bubble — see profiles/PERF_NOTES.md).
-// Norm matches fused_add_rmsnorm semantics: computed over the bf16-rounded sum.
-template <bool F32OUT, bool DELTA_F32, bool HAS_DELTA, int BN, int NIT>
+// ------------------------------------------------ GEMV + residual add
+// r[b][n] = bf16(bf16(dot(x_b, W_n)) + r[b][n]) in place: the O projection
+// with the post-attention residual add in its epilogue. Lane b of the wave
+// that computes output n is the only reader and writer of r[b][n]; its old
+// value is loaded before the dot so it rides along with the W row. Same two
+// roundings as gemv (bf16 out) followed by fused_add_rmsnorm's add, so the
+// same residual bits.
+template <int BN, int NIT>
 __global__ __launch_bounds__(256)
+void gemv_residual_kernel(short* __restrict__ r,           // [BN, N] in/out
+                          const short* __restrict__ x,     // [BN, H]
+                          const short* __restrict__ w,     // [N, H]
+                          int H, int N) {
+  const int wid = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + wid;
+  if (n >= N) return;
+
+  short* rp = r + (long)(lane < BN ? lane : 0) * N + n;
+  const short r_old = *rp;
+  float acc[BN];
+  gemv_row_dot<BN, NIT>(acc, w + (long)n * H, x, H, lane);
+  wave_reduce_sum_n<BN>(acc);
+  float d = acc[0];
+  #pragma unroll
+  for (int b = 1; b < BN; ++b) d = (lane == b) ? acc[b] : d;
+  if (lane < BN) *rp = f2bf(bf2f(f2bf(d)) + bf2f(r_old));
+}
+
+void gemv_residual(torch::Tensor r, torch::Tensor x, torch::Tensor w) {
+  const int B = x.size(0), H = x.size(1), N = w.size(0);
+  TORCH_CHECK(B >= 1 && B <= GEMV_MAXB, "gemv_residual handles B<=8 (decode)");
+  TORCH_CHECK(x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16 &&
+              r.dtype() == torch::kBFloat16);
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && r.is_contiguous());
+  TORCH_CHECK(w.size(1) == H && r.size(0) == B && r.size(1) == N);
+  TORCH_CHECK(H % (WAVE * 8) == 0, "H must be a multiple of 512");
+  hipStream_t s = c10::hip::getCurrentHIPStream();
+  dim3 grid((N + 3) / 4), block(256);
+  #define GEMV_RES2(BN, NIT) hipLaunchKernelGGL( \
+      (gemv_residual_kernel<BN, NIT>), grid, block, 0, s, (short*)r.data_ptr(), \
+      (const short*)x.data_ptr(), (const short*)w.data_ptr(), H, N)
+  #define GEMV_RES(BN) case BN: switch (H / (WAVE * 8)) { \
+    case 4: GEMV_RES2(BN, 4); break; \
+    case 8: GEMV_RES2(BN, 8); break; \
+    default: GEMV_RES2(BN, 0); break; } break;
+  switch (B) {
+    GEMV_RES(1) GEMV_RES(2) GEMV_RES(3) GEMV_RES(4)
+    GEMV_RES(5) GEMV_RES(6) GEMV_RES(7) GEMV_RES(8)
+  }
+  #undef GEMV_RES
+  #undef GEMV_RES2
+  HIP_CHECK_KERNEL();
+}
+
+// ------------------------------------------------ fused add+RMSNorm+GEMV
+// y[B,N] = rmsnorm(x + delta)·γ @ W^T, and (block 0 only) x_out = x + delta:
+// fused_add_rmsnorm (or rmsnorm, without delta) and the projection's gemv in
+// one launch, with their bits.
+//
+// A workgroup is WPB waves, one output row each. Each wave first issues its
+// W-row loads (NIT > 0), so the HBM round trip runs under the norm. The norm
+// is block-cooperative over 4·BN work units (row b, norm wave q): unit (b, q)
+// stands for wave q of the 256-thread block that fused_add_rmsnorm runs on
+// row b, lane for lane (vector v of the row belongs to thread v mod 256), so
+// its sum of squares is that wave's, reduced by the same butterfly; the four
+// per-row sums meet in LDS and combine as block_reduce_sum combines them,
+// (s0+s2)+(s1+s3). No atomics: run-to-run deterministic. With NIT > 0 a
+// unit's (x + delta) vectors stay in registers between the sum and the
+// scaling pass, so each element is read once per workgroup; NIT = 0 re-reads
+// them. The normed rows are staged in LDS once and the dot is gemv_row_dot's
+// from LDS. More waves per workgroup divide the redundant norm reads (every
+// workgroup norms all BN rows) but widen its barriers; 8 is what ships.
+template <int DELTA, int BN, int NIT, int WPB>   // DELTA: 0 none, 1 bf16, 2 f32
+__global__ __launch_bounds__(WPB * WAVE)
 void gemv_addnorm_kernel(void* __restrict__ y,            // [BN, N]
                          const short* __restrict__ x,      // [BN, H]
                          const void* __restrict__ delta_,  // [BN, H] or null
                          short* __restrict__ x_out,        // [BN, H]
                          const short* __restrict__ gamma,  // [H]
                          const short* __restrict__ w,      // [N, H]
-                         int H, int N, float eps) {
+                         int H, int N, float eps, int f32out) {
+  extern __shared__ short xn_sh[];                  // [BN][H] bf16
+  __shared__ float ss_sh[BN][4];
   const int wid = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
-  const int n = blockIdx.x * 4 + wid;
+  const int n = blockIdx.x * WPB + wid;
+  // every wave works on the norm; one past the last row loads row N-1
+  const short* wrow = w + (long)(n < N ? n : N - 1) * H;
 
-  // pass 1 (block-cooperative): row sums of squares, bf16-rounded to match
-  // fused_add_rmsnorm. All 256 threads share the work (a per-wave pass was
-  // measured as a B=5 regression: 4× redundant VALU across the block).
-  __shared__ float ss_sh[BN];
-  if (threadIdx.x < BN) ss_sh[threadIdx.x] = 0.f;
-  __syncthreads();
-  #pragma unroll
-  for (int b = 0; b < BN; ++b) {
-    {
-      float ss = 0.f;
-      for (int base = threadIdx.x * 8; base < H; base += 256 * 8) {
-        bf16x8 xv = *reinterpret_cast<const bf16x8*>(x + (long)b * H + base);
-        #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float v = bf2f(xv[j]);
-          if (HAS_DELTA) {
-            if (DELTA_F32)
-              v += ((const float*)delta_)[(long)b * H + base + j];
-            else
-              v += bf2f(((const short*)delta_)[(long)b * H + base + j]);
-            v = bf2f(f2bf(v));
-          }
-          ss += v * v;
-        }
-      }
-      ss = wave_reduce_sum(ss);
-      if (lane == 0) atomicAdd(&ss_sh[b], ss);
+  constexpr int UNITS = 4 * BN;
+  constexpr int UPW = (UNITS + WPB - 1) / WPB;      // units per wave
+  constexpr int KV = NIT > 0 ? (NIT + 3) / 4 : 1;   // vectors per unit lane
+  // few enough unit vectors per lane to load them all before the W row
+  constexpr bool HOIST = NIT > 0 && UPW * KV <= 4;
+  static_assert(NIT % 4 == 0, "a unit lane holds NIT/4 whole vectors");
+  const int vecs = H / 8;
+
+  // vector v of row b of x and of delta, as loaded
+  struct Raw { bf16x8 x; f32x4 d0, d1; bf16x8 dv; };
+  auto load_raw = [&](int b, int v) {
+    Raw r;
+    r.x = *reinterpret_cast<const bf16x8*>(x + (long)b * H + v * 8);
+    if constexpr (DELTA == 2) {
+      const float* df = (const float*)delta_ + (long)b * H + v * 8;
+      r.d0 = *reinterpret_cast<const f32x4*>(df);
+      r.d1 = *reinterpret_cast<const f32x4*>(df + 4);
+    } else if constexpr (DELTA == 1) {
+      r.dv = *reinterpret_cast<const bf16x8*>(
+          (const short*)delta_ + (long)b * H + v * 8);
     }
-  }
-  __syncthreads();
-  float scale[BN];
-  #pragma unroll
-  for (int b = 0; b < BN; ++b)
-    scale[b] = rsqrtf(ss_sh[b] / H + eps);
-
-  // pass 1.5 (block-cooperative): stage xn = (x+δ)·scale·γ into LDS once, so
-  // the dot loop is lean (w-load + LDS-load + FMA; no per-wave re-add/round)
-  extern __shared__ short xn_sh[];  // [B][H] bf16
-  #pragma unroll
-  for (int b = 0; b < BN; ++b) {
-    {
-      for (int base = threadIdx.x * 8; base < H; base += 256 * 8) {
-        bf16x8 xv = *reinterpret_cast<const bf16x8*>(x + (long)b * H + base);
-        bf16x8 gv = *reinterpret_cast<const bf16x8*>(gamma + base);
-        bf16x8 o;
-        #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float v = bf2f(xv[j]);
-          if (HAS_DELTA) {
-            if (DELTA_F32)
-              v += ((const float*)delta_)[(long)b * H + base + j];
-            else
-              v += bf2f(((const short*)delta_)[(long)b * H + base + j]);
-            v = bf2f(f2bf(v));
-          }
-          o[j] = f2bf(v * scale[b] * bf2f(gv[j]));
-        }
-        *reinterpret_cast<bf16x8*>(&xn_sh[b * H + base]) = o;
-      }
-    }
-  }
-  __syncthreads();
-
-  // block 0 stores the updated residual (other blocks never read x_out here)
-  if (HAS_DELTA && blockIdx.x == 0) {
-    for (int i = threadIdx.x * 8; i < BN * H; i += 256 * 8) {
-      bf16x8 xv = *reinterpret_cast<const bf16x8*>(x + i);
-      bf16x8 o;
+    return r;
+  };
+  // bf16(x + delta): the stored residual
+  auto added = [&](const Raw& r) {
+    if constexpr (DELTA == 0) {
+      return r.x;
+    } else {
+      bf16x8 nr;
       #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        float v = bf2f(xv[j]);
-        if (DELTA_F32) v += ((const float*)delta_)[i + j];
-        else v += bf2f(((const short*)delta_)[i + j]);
-        o[j] = f2bf(v);
+        float d;
+        if constexpr (DELTA == 2) d = j < 4 ? r.d0[j & 3] : r.d1[j & 3];
+        else d = bf2f(r.dv[j]);
+        nr[j] = f2bf(d + bf2f(r.x[j]));
       }
-      *reinterpret_cast<bf16x8*>(x_out + i) = o;
+      return nr;
+    }
+  };
+
+  // Loads return in issue order. With few unit vectors per lane (the model's
+  // shapes) they go out first and the W row right behind them, so the norm
+  // runs while the W row is in flight; otherwise the W row goes first and
+  // the units load one after the other.
+  bf16x8 wv[NIT > 0 ? NIT : 1];
+  Raw raw[HOIST ? UPW : 1][KV];
+  bf16x8 gv[HOIST ? UPW : 1][KV];                   // the units' γ vectors
+  if constexpr (HOIST) {
+    #pragma unroll
+    for (int i = 0; i < UPW; ++i) {
+      const int u = wid + i * WPB;
+      if (u < UNITS) {
+        #pragma unroll
+        for (int k = 0; k < KV; ++k)
+          raw[i][k] = load_raw(u >> 2, (u & 3) * WAVE + lane + k * 4 * WAVE);
+        #pragma unroll
+        for (int k = 0; k < KV; ++k)
+          gv[i][k] = *reinterpret_cast<const bf16x8*>(
+              gamma + ((u & 3) * WAVE + lane + k * 4 * WAVE) * 8);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  gemv_load_w<NIT>(wv, wrow, lane);
+  __builtin_amdgcn_sched_barrier(0);
+
+  // pass 1: each unit's sum of squares -> ss_sh[b][q]
+  bf16x8 nr[UPW][KV];
+  #pragma unroll
+  for (int i = 0; i < UPW; ++i) {
+    const int u = wid + i * WPB;
+    if (u < UNITS) {
+      const int b = u >> 2, q = u & 3;
+      float ss = 0.f;
+      if constexpr (NIT > 0) {
+        #pragma unroll
+        for (int k = 0; k < KV; ++k) {
+          const int v = q * WAVE + lane + k * 4 * WAVE;
+          if constexpr (HOIST) nr[i][k] = added(raw[i][k]);
+          else nr[i][k] = added(load_raw(b, v));
+          ss = sumsq8(ss, nr[i][k]);
+        }
+      } else {
+        for (int v = q * WAVE + lane; v < vecs; v += 4 * WAVE)
+          ss = sumsq8(ss, added(load_raw(b, v)));
+      }
+      ss = wave_reduce_sum(ss);
+      if (lane == 0) ss_sh[b][q] = ss;
     }
   }
+  __syncthreads();
+
+  // pass 2: xn = bf16(r·scale·γ) into LDS; block 0 stores the residual
+  auto scaled = [&](int b, int v, bf16x8 r, bf16x8 g, float scale) {
+    bf16x8 o;
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = f2bf(bf2f(r[j]) * scale * bf2f(g[j]));
+    *reinterpret_cast<bf16x8*>(&xn_sh[b * H + v * 8]) = o;
+    if (DELTA != 0 && blockIdx.x == 0)
+      *reinterpret_cast<bf16x8*>(x_out + (long)b * H + v * 8) = r;
+  };
+  #pragma unroll
+  for (int i = 0; i < UPW; ++i) {
+    const int u = wid + i * WPB;
+    if (u < UNITS) {
+      const int b = u >> 2, q = u & 3;
+      const float scale = rsqrtf(
+          ((ss_sh[b][0] + ss_sh[b][2]) + (ss_sh[b][1] + ss_sh[b][3])) / H + eps);
+      if constexpr (NIT > 0) {
+        #pragma unroll
+        for (int k = 0; k < KV; ++k) {
+          const int v = q * WAVE + lane + k * 4 * WAVE;
+          if constexpr (HOIST) scaled(b, v, nr[i][k], gv[i][k], scale);
+          else scaled(b, v, nr[i][k], *reinterpret_cast<const bf16x8*>(
+                                          gamma + v * 8), scale);
+        }
+      } else {
+        for (int v = q * WAVE + lane; v < vecs; v += 4 * WAVE)
+          scaled(b, v, added(load_raw(b, v)),
+                 *reinterpret_cast<const bf16x8*>(gamma + v * 8), scale);
+      }
+    }
+  }
+  __syncthreads();
   if (n >= N) return;
 
-  // pass 2: lean dot against the LDS-staged normed rows
+  // pass 3: gemv_row_dot against the LDS-staged normed rows
   float acc[BN];
-  gemv_row_dot<BN, NIT>(acc, w + (long)n * H, xn_sh, H, lane);
-  gemv_reduce_store<F32OUT, BN>(acc, y, N, n, lane);
+  gemv_row_dot_w<BN, NIT>(acc, wv, wrow, xn_sh, H, lane);
+  if (f32out) gemv_reduce_store<true, BN>(acc, y, N, n, lane);
+  else gemv_reduce_store<false, BN>(acc, y, N, n, lane);
+}
+
+template <int DELTA, int BN, int NIT>
+static void gemv_addnorm_launch(size_t lds, hipStream_t s, void* y,
+                                const short* x, const void* d, short* x_out,
+                                const short* g, const short* w, int H, int N,
+                                float eps, int f32out) {
+  constexpr int WPB = GEMV_ADDNORM_WPB;
+  // the staged rows plus the kernel's static LDS can pass the 64 KiB a
+  // launch gets without asking (B = 8 at H = 4096)
+  auto k = gemv_addnorm_kernel<DELTA, BN, NIT, WPB>;
+  if (lds + 4 * BN * sizeof(float) > 64 * 1024)
+    TORCH_CHECK(hipFuncSetAttribute((const void*)k,
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess);
+  hipLaunchKernelGGL(k, dim3((N + WPB - 1) / WPB), dim3(WPB * WAVE), lds, s,
+                     y, x, d, x_out, g, w, H, N, eps, f32out);
 }
 
 void gemv_addnorm(torch::Tensor y, torch::Tensor x, torch::Tensor delta,
                   torch::Tensor x_out, torch::Tensor gamma, torch::Tensor w,
                   double eps) {
   const int B = x.size(0), H = x.size(1), N = w.size(0);
-  TORCH_CHECK(B <= GEMV_MAXB && H % (WAVE * 8) == 0);
+  TORCH_CHECK(B >= 1 && B <= GEMV_MAXB && H % (WAVE * 8) == 0 && N >= 1);
   TORCH_CHECK(x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16);
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && y.is_contiguous() &&
+              gamma.is_contiguous() && delta.is_contiguous());
   const bool has_delta = delta.numel() > 0;
-  const bool delta_f32 = has_delta && delta.dtype() == torch::kFloat32;
-  const bool f32out = y.dtype() == torch::kFloat32;
-  dim3 grid((N + 3) / 4), block(256);
+  TORCH_CHECK(!has_delta || (delta.numel() == x.numel() &&
+                             x_out.numel() == x.numel() &&
+                             x_out.data_ptr() != x.data_ptr()));
+  const int dmode = !has_delta ? 0 : delta.dtype() == torch::kFloat32 ? 2 : 1;
+  TORCH_CHECK(dmode != 1 || delta.dtype() == torch::kBFloat16);
+  const int f32out = y.dtype() == torch::kFloat32;
   const size_t lds = (size_t)B * H * sizeof(short);  // staged normed rows
-  TORCH_CHECK(lds <= 160 * 1024, "B*H too large for LDS staging");
+  TORCH_CHECK(lds <= 128 * 1024, "B*H too large for LDS staging");
   hipStream_t s = c10::hip::getCurrentHIPStream();
   const void* dptr = has_delta ? delta.data_ptr() : nullptr;
-  #define LAUNCH_AN2(FO, DF, HD, BN, NIT) hipLaunchKernelGGL( \
-      (gemv_addnorm_kernel<FO, DF, HD, BN, NIT>), grid, block, lds, s, y.data_ptr(), \
-      (const short*)x.data_ptr(), dptr, (short*)x_out.data_ptr(), \
-      (const short*)gamma.data_ptr(), (const short*)w.data_ptr(), \
-      H, N, (float)eps)
-  #define LAUNCH_AN1(FO, DF, HD, BN) do { switch (H / (WAVE * 8)) { \
-    case 4: LAUNCH_AN2(FO, DF, HD, BN, 4); break; \
-    case 8: LAUNCH_AN2(FO, DF, HD, BN, 8); break; \
-    default: LAUNCH_AN2(FO, DF, HD, BN, 0); break; } } while (0)
-  #define LAUNCH_AN(FO, DF, HD) do { switch (B) { \
-    case 1: LAUNCH_AN1(FO, DF, HD, 1); break; \
-    case 2: LAUNCH_AN1(FO, DF, HD, 2); break; \
-    case 3: LAUNCH_AN1(FO, DF, HD, 3); break; \
-    case 4: LAUNCH_AN1(FO, DF, HD, 4); break; \
-    case 5: LAUNCH_AN1(FO, DF, HD, 5); break; \
-    case 6: LAUNCH_AN1(FO, DF, HD, 6); break; \
-    case 7: LAUNCH_AN1(FO, DF, HD, 7); break; \
-    default: LAUNCH_AN1(FO, DF, HD, 8); break; } } while (0)
-  if (!has_delta) {
-    if (f32out) LAUNCH_AN(true, false, false); else LAUNCH_AN(false, false, false);
-  } else if (delta_f32) {
-    if (f32out) LAUNCH_AN(true, true, true); else LAUNCH_AN(false, true, true);
-  } else {
-    if (f32out) LAUNCH_AN(true, false, true); else LAUNCH_AN(false, false, true);
-  }
-  #undef LAUNCH_AN
-  #undef LAUNCH_AN1
-  #undef LAUNCH_AN2
+  #define AN_GO(D, BN, NIT) gemv_addnorm_launch<D, BN, NIT>( \
+      lds, s, y.data_ptr(), (const short*)x.data_ptr(), dptr, \
+      (short*)x_out.data_ptr(), (const short*)gamma.data_ptr(), \
+      (const short*)w.data_ptr(), H, N, (float)eps, f32out)
+  #define AN_NIT(D, BN) do { switch (H / (WAVE * 8)) { \
+    case 4: AN_GO(D, BN, 4); break; \
+    case 8: AN_GO(D, BN, 8); break; \
+    default: AN_GO(D, BN, 0); break; } } while (0)
+  #define AN_B(D) do { switch (B) { \
+    case 1: AN_NIT(D, 1); break; case 2: AN_NIT(D, 2); break; \
+    case 3: AN_NIT(D, 3); break; case 4: AN_NIT(D, 4); break; \
+    case 5: AN_NIT(D, 5); break; case 6: AN_NIT(D, 6); break; \
+    case 7: AN_NIT(D, 7); break; default: AN_NIT(D, 8); break; } } while (0)
+  if (dmode == 0) AN_B(0); else if (dmode == 1) AN_B(1); else AN_B(2);
+  #undef AN_B
+  #undef AN_NIT
+  #undef AN_GO
   HIP_CHECK_KERNEL();
 }

@@ -160,9 +160,8 @@ void router_gemv_partial_kernel(float* __restrict__ yp,   // [B, N, RS]
     #pragma unroll
     for (int b = 0; b < 8; ++b) {
       if (b < B) {
-        bf16x8 xv = *reinterpret_cast<const bf16x8*>(x + (long)b * H + h0 + base);
-        #pragma unroll
-        for (int j = 0; j < 8; ++j) acc[b] += wf[j] * bf2f(xv[j]);
+        acc[b] = dot8_unfused(acc[b], wf, *reinterpret_cast<const bf16x8*>(
+            x + (long)b * H + h0 + base));
       }
     }
   }
@@ -172,6 +171,104 @@ void router_gemv_partial_kernel(float* __restrict__ yp,   // [B, N, RS]
       const float r = wave_reduce_sum(acc[b]);
       if (lane == 0) yp[((long)b * N + n) * RS + s] = r;
     }
+  }
+}
+
+// router_gemv_partial with the post-attention RMSNorm folded in: the input is
+// the residual row r[b], not a normed row. One wave per (expert row n, batch
+// row b), grid (N/4, B). The wave loads r[b], γ and its W row up front; while
+// the cold W row is in flight it computes the row's sum of squares in the
+// order rmsnorm's 256-thread block does (vector v belongs to thread v mod 256:
+// accumulator q stands for that block's wave q, lane for lane; each is
+// reduced by the same butterfly and they combine as block_reduce_sum combines
+// four waves), forms xn = bf16(r·scale·γ) as the norm kernel does, and takes
+// the RS quarter dots with router_gemv_partial's lane → element mapping. So
+// yp, and hbuf (stored by the n = 0 wave of each b, for moe_gemv_h), hold the
+// bits of rmsnorm → router_gemv_partial. H2048: every load issued before the
+// first use; otherwise any H with H % 32 == 0, loads inside the loops.
+template <bool H2048>
+__global__ __launch_bounds__(256)
+void router_norm_gemv_partial_kernel(float* __restrict__ yp,   // [B, N, RS]
+                                     short* __restrict__ hbuf, // [B, H]
+                                     const short* __restrict__ r,     // [B, H]
+                                     const short* __restrict__ gamma, // [H]
+                                     const short* __restrict__ w,     // [N, H]
+                                     int H, int N, float eps) {
+  const int wid = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  const int n = blockIdx.x * 4 + wid;
+  const int b = blockIdx.y;
+  if (n >= N) return;
+  const bool store_h = n == 0;
+  const short* wrow = w + (long)n * H;
+  const short* rrow = r + (long)b * H;
+  short* hrow = hbuf + (long)b * H;
+  float ss[RS], acc[RS];
+  #pragma unroll
+  for (int q = 0; q < RS; ++q) { ss[q] = 0.f; acc[q] = 0.f; }
+
+  // xn = bf16(r·scale·γ) for one vector; its quarter-dot step against wv
+  auto norm_dot = [&](float a, bf16x8 rv, bf16x8 gv, bf16x8 wv, float scale,
+                      int off) {
+    bf16x8 xn;
+    float wf[8];
+    #pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      xn[j] = f2bf(bf2f(rv[j]) * scale * bf2f(gv[j]));
+      wf[j] = bf2f(wv[j]);
+    }
+    if (store_h) *reinterpret_cast<bf16x8*>(hrow + off) = xn;
+    return dot8_unfused(a, wf, xn);
+  };
+
+  if constexpr (H2048) {
+    bf16x8 wv[RS], rv[RS], gv[RS];
+    // loads return in issue order: r and γ (L2 hits) go first so the norm
+    // runs while the W row (cold, HBM) is still in flight behind them
+    #pragma unroll
+    for (int q = 0; q < RS; ++q)
+      rv[q] = *reinterpret_cast<const bf16x8*>(rrow + (q * WAVE + lane) * 8);
+    #pragma unroll
+    for (int q = 0; q < RS; ++q)
+      gv[q] = *reinterpret_cast<const bf16x8*>(gamma + (q * WAVE + lane) * 8);
+    __builtin_amdgcn_sched_barrier(0);
+    #pragma unroll
+    for (int q = 0; q < RS; ++q)
+      wv[q] = *reinterpret_cast<const bf16x8*>(wrow + (q * WAVE + lane) * 8);
+    __builtin_amdgcn_sched_barrier(0);
+    #pragma unroll
+    for (int q = 0; q < RS; ++q) ss[q] = sumsq8(0.f, rv[q]);
+    wave_reduce_sum_n<RS>(ss);
+    const float scale = rsqrtf(((ss[0] + ss[2]) + (ss[1] + ss[3])) / H + eps);
+    #pragma unroll
+    for (int q = 0; q < RS; ++q)
+      acc[q] = norm_dot(0.f, rv[q], gv[q], wv[q], scale, (q * WAVE + lane) * 8);
+  } else {
+    const int vecs = H / 8;
+    #pragma unroll
+    for (int q = 0; q < RS; ++q)
+      for (int v = q * WAVE + lane; v < vecs; v += 4 * WAVE)
+        ss[q] = sumsq8(ss[q], *reinterpret_cast<const bf16x8*>(rrow + v * 8));
+    wave_reduce_sum_n<RS>(ss);
+    const float scale = rsqrtf(((ss[0] + ss[2]) + (ss[1] + ss[3])) / H + eps);
+    const int hs = H / RS;
+    #pragma unroll
+    for (int q = 0; q < RS; ++q)
+      for (int base = lane * 8; base < hs; base += WAVE * 8) {
+        const int off = q * hs + base;
+        acc[q] = norm_dot(acc[q],
+                          *reinterpret_cast<const bf16x8*>(rrow + off),
+                          *reinterpret_cast<const bf16x8*>(gamma + off),
+                          *reinterpret_cast<const bf16x8*>(wrow + off), scale,
+                          off);
+      }
+  }
+  wave_reduce_sum_n<RS>(acc);
+  if (lane == 0) {
+    f32x4 o;
+    #pragma unroll
+    for (int q = 0; q < RS; ++q) o[q] = acc[q];
+    *reinterpret_cast<f32x4*>(yp + ((long)b * N + n) * RS) = o;
   }
 }
 
@@ -345,6 +442,19 @@ void moe_router(torch::Tensor topk_ids, torch::Tensor topk_w, torch::Tensor logi
   HIP_CHECK_KERNEL();
 }
 
+// persistent RS-partial logits buffer per (B, E): allocation-free on graph
+// replay
+static float* router_partials(int B, int E, c10::Device dev) {
+  static std::unordered_map<long, torch::Tensor> parts;
+  const long key = (long)B * 1024 + E;
+  auto it = parts.find(key);
+  if (it == parts.end())
+    it = parts.emplace(key, torch::empty(
+        {(long)B * E * RS},
+        torch::TensorOptions().device(dev).dtype(torch::kFloat32))).first;
+  return it->second.data_ptr<float>();
+}
+
 void router_gemv_topk(torch::Tensor topk_ids, torch::Tensor topk_w,
                       torch::Tensor x, torch::Tensor wr, int64_t K) {
   const int B = x.size(0), H = x.size(1), E = wr.size(0);
@@ -353,23 +463,48 @@ void router_gemv_topk(torch::Tensor topk_ids, torch::Tensor topk_w,
               "H/RS must be a multiple of 8");
   TORCH_CHECK(x.dtype() == torch::kBFloat16 && wr.dtype() == torch::kBFloat16);
   TORCH_CHECK(x.is_contiguous() && wr.is_contiguous());
-  // persistent partial buffer per (B, E): allocation-free on graph replay
-  static std::unordered_map<long, torch::Tensor> parts;
-  const long key = (long)B * 1024 + E;
-  auto it = parts.find(key);
-  if (it == parts.end())
-    it = parts.emplace(key, torch::empty(
-        {(long)B * E * RS},
-        torch::TensorOptions().device(x.device()).dtype(torch::kFloat32))).first;
+  float* yp = router_partials(B, E, x.device());
   hipStream_t s = c10::hip::getCurrentHIPStream();
   dim3 g1((E + 3) / 4, RS);
   hipLaunchKernelGGL(router_gemv_partial_kernel, g1, dim3(256), 0, s,
-                     it->second.data_ptr<float>(), (const short*)x.data_ptr(),
+                     yp, (const short*)x.data_ptr(),
                      (const short*)wr.data_ptr(), B, H, E);
   HIP_CHECK_KERNEL();
   hipLaunchKernelGGL(moe_router_p4_kernel, dim3(B), dim3(WAVE), 0, s,
                      topk_ids.data_ptr<int>(), topk_w.data_ptr<float>(),
-                     it->second.data_ptr<float>(), E, (int)K);
+                     yp, E, (int)K);
+  HIP_CHECK_KERNEL();
+}
+
+void router_norm_gemv_topk(torch::Tensor topk_ids, torch::Tensor topk_w,
+                           torch::Tensor hbuf, torch::Tensor r,
+                           torch::Tensor gamma, torch::Tensor wr, int64_t K,
+                           double eps) {
+  const int B = r.size(0), H = r.size(1), E = wr.size(0);
+  TORCH_CHECK(E <= 128 && K >= 1 && K <= 8 && K <= E && B >= 1 && B <= 8);
+  TORCH_CHECK(H % (RS * 8) == 0, "H/RS must be a multiple of 8");
+  TORCH_CHECK(r.dtype() == torch::kBFloat16 && wr.dtype() == torch::kBFloat16 &&
+              gamma.dtype() == torch::kBFloat16 &&
+              hbuf.dtype() == torch::kBFloat16);
+  TORCH_CHECK(r.is_contiguous() && wr.is_contiguous() && hbuf.is_contiguous() &&
+              gamma.is_contiguous());
+  TORCH_CHECK(wr.size(1) == H && gamma.numel() == H && hbuf.size(0) == B &&
+              hbuf.size(1) == H);
+  TORCH_CHECK(topk_ids.numel() == (long)B * K && topk_w.numel() == (long)B * K);
+  float* yp = router_partials(B, E, r.device());
+  hipStream_t s = c10::hip::getCurrentHIPStream();
+  dim3 g1((E + 3) / 4, B);
+  #define ROUTER_NORM(H2048) hipLaunchKernelGGL( \
+      router_norm_gemv_partial_kernel<H2048>, g1, dim3(256), 0, s, yp, \
+      (short*)hbuf.data_ptr(), (const short*)r.data_ptr(), \
+      (const short*)gamma.data_ptr(), (const short*)wr.data_ptr(), H, E, \
+      (float)eps)
+  if (H == RS * WAVE * 8) ROUTER_NORM(true); else ROUTER_NORM(false);
+  #undef ROUTER_NORM
+  HIP_CHECK_KERNEL();
+  hipLaunchKernelGGL(moe_router_p4_kernel, dim3(B), dim3(WAVE), 0, s,
+                     topk_ids.data_ptr<int>(), topk_w.data_ptr<float>(),
+                     yp, E, (int)K);
   HIP_CHECK_KERNEL();
 }
 

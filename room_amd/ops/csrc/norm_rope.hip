@@ -24,9 +24,7 @@ __global__ void rmsnorm_kernel(short* __restrict__ out,
   float sumsq = 0.f;
   const int vecs = cols / 8;
   for (int i = threadIdx.x; i < vecs; i += blockDim.x) {
-    bf16x8 v = *reinterpret_cast<const bf16x8*>(x + i * 8);
-    #pragma unroll
-    for (int j = 0; j < 8; ++j) { float f = bf2f(v[j]); sumsq += f * f; }
+    sumsq = sumsq8(sumsq, *reinterpret_cast<const bf16x8*>(x + i * 8));
   }
   float total = block_reduce_sum(sumsq, red);
   float scale = rsqrtf(total / cols + eps);
@@ -73,12 +71,8 @@ __global__ void fused_add_rmsnorm_kernel(short* __restrict__ out,
       for (int j = 0; j < 8; ++j) xv[j] = bf2f(v[j]);
     }
     #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float f = xv[j] + bf2f(rv[j]);
-      nr[j] = f2bf(f);
-      float g = bf2f(nr[j]);         // norm over the *stored* bf16 residual
-      sumsq += g * g;
-    }
+    for (int j = 0; j < 8; ++j) nr[j] = f2bf(xv[j] + bf2f(rv[j]));
+    sumsq = sumsq8(sumsq, nr);       // norm over the *stored* bf16 residual
     *reinterpret_cast<bf16x8*>(r + i * 8) = nr;
   }
   float total = block_reduce_sum(sumsq, red);

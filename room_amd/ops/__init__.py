@@ -124,8 +124,10 @@ def flash_prefill(out: torch.Tensor, q: torch.Tensor, kcache: torch.Tensor,
                   vcache: torch.Tensor, block_table: torch.Tensor,
                   seq_ids: torch.Tensor, q_pos: torch.Tensor,
                   tile_desc: torch.Tensor, scale: float) -> torch.Tensor:
-    """MFMA flash prefill; tile_desc [G,2] = (row0, n_tokens≤16), one sequence
-    per tile (build with build_qtile_desc)."""
+    """MFMA flash prefill; tile_desc [G,2] = (row0, n_tokens≤32), one sequence
+    per tile (build with build_qtile_desc). q may be a row-strided view of
+    the packed qkv; out, the caches, the block table and the int32 vectors
+    must be contiguous (checked by the wrapper)."""
     _require().flash_prefill(out, q, kcache, vcache, block_table, seq_ids,
                              q_pos, tile_desc, scale)
     return out

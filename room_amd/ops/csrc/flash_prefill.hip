@@ -249,8 +249,33 @@ void flash_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
                    torch::Tensor seq_ids, torch::Tensor q_pos,
                    torch::Tensor tile_desc, double scale) {
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16);
-  TORCH_CHECK(q.size(-1) == FP_D);
+  TORCH_CHECK(q.dim() == 3 && q.size(-1) == FP_D, "q is [T, Hq, 128]");
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == FP_D);  // strided row-views OK
+  // everything the kernel indexes is checked here: a wrong shape must be a
+  // Python error, never an out-of-bounds access
+  TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kBFloat16 &&
+              out.is_contiguous() && out.sizes() == q.sizes(),
+              "out must be contiguous bf16 shaped like q");
+  TORCH_CHECK(kcache.is_cuda() && vcache.is_cuda() &&
+              kcache.dtype() == torch::kBFloat16 &&
+              vcache.dtype() == torch::kBFloat16 &&
+              kcache.is_contiguous() && vcache.is_contiguous(),
+              "caches must be contiguous bf16");
+  TORCH_CHECK(kcache.dim() == 4 && kcache.size(2) == FP_BS &&
+              kcache.size(3) == FP_D && vcache.sizes() == kcache.sizes(),
+              "caches are [NB, Hk, 16, 128] and equally shaped");
+  TORCH_CHECK(tile_desc.is_cuda() && tile_desc.dtype() == torch::kInt32 &&
+              tile_desc.dim() == 2 && tile_desc.size(1) == 2 &&
+              tile_desc.is_contiguous(), "tile_desc is contiguous int32 [G, 2]");
+  TORCH_CHECK(seq_ids.is_cuda() && q_pos.is_cuda() &&
+              seq_ids.dtype() == torch::kInt32 &&
+              q_pos.dtype() == torch::kInt32 &&
+              seq_ids.is_contiguous() && q_pos.is_contiguous() &&
+              seq_ids.numel() == q.size(0) && q_pos.numel() == q.size(0),
+              "seq_ids and q_pos are int32 with one entry per q row");
+  TORCH_CHECK(block_table.is_cuda() && block_table.dtype() == torch::kInt32 &&
+              block_table.dim() == 2 && block_table.is_contiguous(),
+              "block_table is contiguous int32 [seqs, max_blocks]");
   const int n_kvheads = kcache.size(1);
   TORCH_CHECK(q.size(1) == n_kvheads * FP_QH);
   const int G = tile_desc.size(0);

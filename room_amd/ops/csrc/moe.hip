@@ -675,6 +675,22 @@ void moe_grouped_gemm128(torch::Tensor out, torch::Tensor x, torch::Tensor w,
   const int H = x.size(-1), N = out.size(-1);
   const int G = tile_desc.size(0);
   TORCH_CHECK(H % G2_BK == 0 && N % G2_BN == 0);
+  // a wrong shape must be a Python error, never an out-of-bounds access
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && out.is_cuda() &&
+              x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16 &&
+              out.dtype() == torch::kBFloat16, "x, w and out must be bf16");
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous(),
+              "x, w and out must be contiguous");
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2, "x is [T, H], out is [P, N]");
+  TORCH_CHECK(w.dim() == 3 && w.size(1) == N && w.size(2) == H,
+              "w is [E, N, H]");
+  TORCH_CHECK(pair_token.is_cuda() && pair_token.dtype() == torch::kInt32 &&
+              pair_token.is_contiguous() &&
+              pair_token.numel() == out.size(0),
+              "pair_token is int32 with one entry per out row");
+  TORCH_CHECK(tile_desc.is_cuda() && tile_desc.dtype() == torch::kInt32 &&
+              tile_desc.dim() == 2 && tile_desc.is_contiguous(),
+              "tile_desc is contiguous int32 [G, 3]");
   TORCH_CHECK(tile_desc.size(1) == 3, "desc is [G,3]; n-tile comes from grid.y");
   hipStream_t s = c10::hip::getCurrentHIPStream();
   dim3 grid(G, N / G2_BN), block(512);
@@ -719,6 +735,20 @@ void moe_combine_gather(torch::Tensor out, torch::Tensor z, torch::Tensor topk_w
   const int T = out.size(0), H = out.size(-1);
   const int K = topk_w.size(-1);
   TORCH_CHECK(K <= 8 && out.dtype() == torch::kBFloat16);
+  // a wrong shape must be a Python error, never an out-of-bounds access
+  TORCH_CHECK(out.is_cuda() && out.dim() == 2 && out.is_contiguous(),
+              "out is contiguous [T, H]");
+  TORCH_CHECK(z.is_cuda() && z.dtype() == torch::kBFloat16 &&
+              z.is_contiguous() && z.dim() == 2 && z.size(1) == H,
+              "z is contiguous bf16 [P, H]");
+  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
+  TORCH_CHECK(topk_w.is_cuda() && topk_w.dtype() == torch::kFloat32 &&
+              topk_w.dim() == 2 && topk_w.size(0) == T && K >= 1 &&
+              topk_w.is_contiguous(), "topk_w is contiguous f32 [T, K]");
+  TORCH_CHECK(inv_order.is_cuda() && inv_order.dtype() == torch::kInt32 &&
+              inv_order.is_contiguous() &&
+              inv_order.numel() == (int64_t)T * K,
+              "inv_order is int32 with T*K entries");
   dim3 grid(T), block(256);
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(moe_combine_gather_kernel, grid, block, 0, s,

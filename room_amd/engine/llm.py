@@ -73,6 +73,18 @@ def expert_dtype_from_env(environ=os.environ) -> str:
     return v
 
 
+def expert_image_from_env(environ=os.environ) -> bool:
+    """Whether an fp8 engine keeps the bf16 image of its expert weights, from
+    ROOMAMD_EXPERT_IMAGE: unset, empty or "1" keeps it (prefill reads the
+    image), "0" drops it (prefill reads the e4m3 weights; fp8 only)."""
+    v = environ.get("ROOMAMD_EXPERT_IMAGE", "").strip()
+    if v in ("", "1"):
+        return True
+    if v == "0":
+        return False
+    raise ValueError(f"ROOMAMD_EXPERT_IMAGE must be 0 or 1, got {v!r}")
+
+
 class LocalEngine:
     """ChatEngine implementation running qwen3-coder-30b on this GPU."""
 
@@ -95,9 +107,16 @@ class LocalEngine:
             self.device = torch.device("cuda", torch.cuda.current_device())
         # expert-weight storage, read here once (docs/CONFIG.md)
         self.expert_dtype = expert_dtype_from_env()
+        self.expert_image = expert_image_from_env()
+        if not self.expert_image and self.expert_dtype != "fp8":
+            raise ValueError(
+                "ROOMAMD_EXPERT_IMAGE=0 needs ROOMAMD_EXPERT_DTYPE=fp8: with "
+                f"{self.expert_dtype} expert weights the bf16 tensors are the "
+                "only copy, there is no image to drop")
         t0 = time.time()
         self.model = Qwen3MoEModel(cfg, self.device, seed=seed,
-                                   expert_dtype=self.expert_dtype)
+                                   expert_dtype=self.expert_dtype,
+                                   expert_image=self.expert_image)
         self.load_seconds = time.time() - t0
 
         bpb = PagedKVCache.bytes_per_block(cfg.num_layers, cfg.num_kv_heads,

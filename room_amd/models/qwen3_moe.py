@@ -10,7 +10,9 @@ every projection (QKV/O/router/lm_head) runs on the hand-written GEMVs; wide
 decode (9-64 rows) runs them and the MoE on the skinny MFMA GEMM;
 prefill's large GEMMs go through hipBLASLt via torch.nn.functional.linear.
 With expert_dtype="fp8" (opt-in) the expert weights are also held as
-block-scaled e4m3 and both decode paths read those (ops/csrc/moe_fp8.hip).
+block-scaled e4m3 and both decode paths read those (ops/csrc/moe_fp8.hip);
+with expert_image=False on top they are held ONLY as e4m3 and prefill's
+grouped GEMM reads them too.
 
 Inference-only (no autograd); a training path is out of scope for the
 reference's semantics (it never trains).
@@ -105,9 +107,21 @@ class _Step:
     moe_out: torch.Tensor | None = None     # [T, H]
 
 
+def _check_expert_args(expert_dtype: str, expert_image: bool) -> None:
+    if expert_dtype not in EXPERT_DTYPES:
+        raise ValueError(f"expert_dtype must be one of {EXPERT_DTYPES}, "
+                         f"got {expert_dtype!r}")
+    if not expert_image and expert_dtype != "fp8":
+        raise ValueError('expert_image=False needs expert_dtype="fp8": with '
+                         f"{expert_dtype} experts the bf16 tensors are the "
+                         "only copy of the weights")
+
+
 class Qwen3MoELayer:
     def __init__(self, cfg: Qwen3MoEConfig, device: torch.device,
-                 gen: torch.Generator, expert_dtype: str = "bf16"):
+                 gen: torch.Generator, expert_dtype: str = "bf16",
+                 expert_image: bool = True):
+        _check_expert_args(expert_dtype, expert_image)
         h, d = cfg.hidden_size, cfg.head_dim
         qdim = cfg.num_q_heads * d
         kvdim = cfg.num_kv_heads * d
@@ -124,6 +138,18 @@ class Qwen3MoELayer:
         self.wqkv = rnd(qdim + 2 * kvdim, h)      # fused QKV projection
         self.wo = rnd(h, qdim)
         self.router_w = rnd(cfg.num_experts, h)
+        if not expert_image:
+            # fp8 only: each bf16 tensor is quantised and released before the
+            # next is drawn (same generator order as the image build), and
+            # the layer gets no w13 / w2 attribute at all, so no bf16 path
+            # can run on it by accident
+            w = rnd(cfg.num_experts, 2 * cfg.moe_intermediate_size, h)
+            self.w13_q, self.w13_s = quantize_fp8_block(w)
+            del w
+            w = rnd(cfg.num_experts, h, cfg.moe_intermediate_size)
+            self.w2_q, self.w2_s = quantize_fp8_block(w)
+            del w
+            return
         self.w13 = rnd(cfg.num_experts, 2 * cfg.moe_intermediate_size, h)
         self.w2 = rnd(cfg.num_experts, h, cfg.moe_intermediate_size)
         if expert_dtype == "fp8":
@@ -142,15 +168,17 @@ class Qwen3MoEModel:
     """Flat-tensor model (no nn.Module overhead on the decode path)."""
 
     def __init__(self, cfg: Qwen3MoEConfig, device: str | torch.device = "cuda",
-                 seed: int = 1234, expert_dtype: str = "bf16"):
-        if expert_dtype not in EXPERT_DTYPES:
-            raise ValueError(f"expert_dtype must be one of {EXPERT_DTYPES}, "
-                             f"got {expert_dtype!r}")
+                 seed: int = 1234, expert_dtype: str = "bf16",
+                 expert_image: bool = True):
+        _check_expert_args(expert_dtype, expert_image)
         self.cfg = cfg
         # "fp8": expert weights also held as e4m3 with a scale per 128x128
         # block, read by the decode paths (narrow GEMVs, wide skinny GEMM);
         # prefill reads their exact bf16 image
         self.expert_dtype = expert_dtype
+        # False (fp8 only): no bf16 image; prefill's grouped GEMM reads the
+        # e4m3 weights (moe_grouped_gemm128_fp8) with the image path's bits
+        self.expert_image = bool(expert_image)
         self.device = torch.device(device)
         gen = torch.Generator(device=self.device)
         gen.manual_seed(seed)
@@ -158,7 +186,8 @@ class Qwen3MoEModel:
         self.embed = torch.empty(cfg.vocab_size, h, dtype=torch.bfloat16,
                                  device=self.device).normal_(0, 0.02, generator=gen)
         # one layer at a time: the quantiser's f32 transients stay per-layer
-        self.layers = [Qwen3MoELayer(cfg, self.device, gen, expert_dtype)
+        self.layers = [Qwen3MoELayer(cfg, self.device, gen, expert_dtype,
+                                     self.expert_image)
                        for _ in range(cfg.num_layers)]
         self.final_norm_w = torch.ones(h, dtype=torch.bfloat16, device=self.device)
         self.lm_head = torch.empty(cfg.vocab_size, h, dtype=torch.bfloat16,
@@ -184,9 +213,11 @@ class Qwen3MoEModel:
 
     def num_params(self) -> int:
         cfg = self.cfg
-        per_layer = (self.layers[0].wqkv.numel() + self.layers[0].wo.numel()
-                     + self.layers[0].router_w.numel() + self.layers[0].w13.numel()
-                     + self.layers[0].w2.numel())
+        l0 = self.layers[0]
+        w13, w2 = ((l0.w13, l0.w2) if self.expert_image
+                   else (l0.w13_q, l0.w2_q))
+        per_layer = (l0.wqkv.numel() + l0.wo.numel() + l0.router_w.numel()
+                     + w13.numel() + w2.numel())
         return self.embed.numel() + self.lm_head.numel() + cfg.num_layers * per_layer
 
     def _dense(self, x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
@@ -517,13 +548,22 @@ class Qwen3MoEModel:
         inv_order[order] = torch.arange(P, device=hbuf.device)
         inv_order = inv_order.int().contiguous()
         desc = ops.moe_build_desc_device(pair_expert, cfg.num_experts)
+        lean = not self.expert_image      # fp8 without the bf16 image
         gateup = torch.empty(P, 2 * I, dtype=torch.bfloat16, device=hbuf.device)
-        ops.moe_grouped_gemm128(gateup, hbuf, layer.w13, pair_token, desc)
+        if lean:
+            ops.moe_grouped_gemm128_fp8(gateup, hbuf, layer.w13_q,
+                                        layer.w13_s, pair_token, desc)
+        else:
+            ops.moe_grouped_gemm128(gateup, hbuf, layer.w13, pair_token, desc)
         h = torch.empty(P, I, dtype=torch.bfloat16, device=hbuf.device)
         ops.silu_mul(h, gateup)
         z = torch.empty(P, H, dtype=torch.bfloat16, device=hbuf.device)
         # the down GEMM reads h rows per sorted pair: identity pair map
-        ops.moe_grouped_gemm128(z, h, layer.w2, st.pair_row, desc)
+        if lean:
+            ops.moe_grouped_gemm128_fp8(z, h, layer.w2_q, layer.w2_s,
+                                        st.pair_row, desc)
+        else:
+            ops.moe_grouped_gemm128(z, h, layer.w2, st.pair_row, desc)
         out_bf = torch.empty(T, H, dtype=torch.bfloat16, device=hbuf.device)
         ops.moe_combine_gather(out_bf, z, topk_w.contiguous(), inv_order)
         return out_bf

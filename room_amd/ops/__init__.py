@@ -285,6 +285,22 @@ def moe_grouped_gemm_skinny_fp8(out: torch.Tensor, x: torch.Tensor,
     return out
 
 
+def moe_grouped_gemm128_fp8(out: torch.Tensor, x: torch.Tensor,
+                            w_q: torch.Tensor, w_s: torch.Tensor,
+                            pair_token: torch.Tensor, tile_desc: torch.Tensor
+                            ) -> torch.Tensor:
+    """moe_grouped_gemm128 on fp8 weights (prefill): out [P, N] bf16, x [T, K]
+    bf16, w_q [E, N, K] float8_e4m3fn, w_s [E, N/128, K/128] f32, tile_desc
+    from moe_build_desc_device(..., bm=128). A weight tile is staged as
+    bf16_rne(f32(q) · s) and then runs the bf16 kernel's MFMA sequence, so out
+    equals moe_grouped_gemm128 on dequantize_fp8_block(w_q, w_s).to(bf16) bit
+    for bit (unlike the decode fp8 kernels, which scale f32 partial sums).
+    Allocates nothing."""
+    _require().moe_grouped_gemm128_fp8(out, x, w_q, w_s, pair_token,
+                                       tile_desc)
+    return out
+
+
 def moe_desc_gmax(num_pairs: int, num_experts: int, bm: int = 128) -> int:
     """Descriptor rows that always suffice: every expert can end in one
     ragged tile on top of the ceil(P/bm) full ones."""

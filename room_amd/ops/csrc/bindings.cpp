@@ -53,6 +53,10 @@ void moe_grouped_gemm_skinny_fp8(torch::Tensor out, torch::Tensor x,
                                  torch::Tensor w_q, torch::Tensor w_s,
                                  torch::Tensor pair_token,
                                  torch::Tensor tile_desc);
+void moe_grouped_gemm128_fp8(torch::Tensor out, torch::Tensor x,
+                             torch::Tensor w_q, torch::Tensor w_s,
+                             torch::Tensor pair_token,
+                             torch::Tensor tile_desc);
 void paged_attention_split(torch::Tensor out, torch::Tensor q,
                            torch::Tensor kcache, torch::Tensor vcache,
                            torch::Tensor block_table, torch::Tensor seq_ids,
@@ -125,6 +129,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MoE down GEMV + weighted scatter-add, block-scaled e4m3 weights");
   m.def("moe_grouped_gemm_skinny_fp8", &moe_grouped_gemm_skinny_fp8,
         "BM=16 grouped MFMA GEMM, block-scaled e4m3 weights (wide decode)");
+  m.def("moe_grouped_gemm128_fp8", &moe_grouped_gemm128_fp8,
+        "BM=128 grouped MFMA GEMM, block-scaled e4m3 weights (prefill)");
   m.def("attn_nsplits", &attn_nsplits, "NSPLITS constant");
   m.def("paged_attention_split", &paged_attention_split,
         "split-KV flash-decode paged attention");

@@ -564,6 +564,7 @@ void moe_gemv_down(torch::Tensor out, torch::Tensor h, torch::Tensor w2,
 //   B (32×16): lane l holds B[(l>>4)*8 .. +8][l&15]
 //   C (16×16): lane l, reg r ↦ row (l>>4)*4 + r, col l&15
 typedef __attribute__((ext_vector_type(4))) float cfrag_t;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 // A BM=16 tile re-reads each expert's weight panel ceil(rows/16)× per layer
 // (~8× at 2k-token prefill → 6.4 GB/layer). BM=128 reads W once per expert
@@ -578,11 +579,21 @@ typedef __attribute__((ext_vector_type(4))) float cfrag_t;
 // Only <G2_BM, G2_BN, G2_BK> is instantiated. BN=128 (half the X-tile
 // re-reads), BK=128 and BM=256 were each measured no faster; see
 // profiles/PERF_NOTES.md.
-template <int BM, int BN, int BK = G2_BK>
+//
+// W8 = true (moe_grouped_gemm128_fp8): w holds e4m3fn bytes, w_s one f32
+// scale per 128x128 block [E, N/128, H/128]. Only the W staging differs: a
+// thread loads 8 B = 8 k of one row, and the tile reaches LDS as
+// bf16_rne(f32(q) * s), the bits of dequantize_fp8_block(...).to(bf16). A
+// 64-column n-tile and a 64-wide k-step lie inside one scale block, so s is
+// one workgroup-uniform load per k-step. From LDS on (MFMA order, epilogue)
+// both instantiations run the same code: the outputs are bit-equal to the
+// bf16 kernel on the dequantised weights.
+template <int BM, int BN, int BK = G2_BK, bool W8 = false>
 __global__ __launch_bounds__(512)
 void moe_grouped_gemm128_kernel(short* __restrict__ out,      // [P, N]
                                 const short* __restrict__ x,   // [T, H]
-                                const short* __restrict__ w,   // [E, N, H]
+                                const void* __restrict__ wv,   // [E, N, H]
+                                const float* __restrict__ w_s, // W8 only
                                 const int* __restrict__ pair_token,
                                 const int* __restrict__ tile_desc,  // [G,3]
                                 int H, int N) {
@@ -600,7 +611,13 @@ void moe_grouped_gemm128_kernel(short* __restrict__ out,      // [P, N]
   __shared__ short xs[BM][BK + G2_PAD];
   __shared__ short ws[BN][BK + G2_PAD];
 
-  const short* wbase = w + (long)e * N * H;
+  // bf16: the expert's panel; W8: the same panel, one byte per element
+  const short* wbase = W8 ? nullptr
+                          : reinterpret_cast<const short*>(wv) + (long)e * N * H;
+  const uint8_t* qbase = W8
+      ? reinterpret_cast<const uint8_t*>(wv) + (long)e * N * H : nullptr;
+  const float* sbase = W8
+      ? w_s + ((long)e * (N / 128) + n0 / 128) * (H / 128) : nullptr;
   constexpr int NF = BN / 16;             // n-fragments per wave
   constexpr int MF = BM / 128;            // m-fragments per wave (1 or 2)
 
@@ -630,8 +647,25 @@ void moe_grouped_gemm128_kernel(short* __restrict__ out,      // [P, N]
       const int idx = tid + it * 512;
       const int r = (idx * 8) / BK;
       const int c = (idx * 8) % BK;
-      bf16x8 v = *reinterpret_cast<const bf16x8*>(
-          wbase + (long)(n0 + r) * H + k0 + c);
+      bf16x8 v;
+      if constexpr (W8) {
+        // 8 e4m3 bytes -> f32 (exact) -> one multiply by the block scale ->
+        // bf16 round-to-nearest-even
+        const int2 q = *reinterpret_cast<const int2*>(
+            qbase + (long)(n0 + r) * H + k0 + c);
+        const float sc = sbase[k0 / 128];
+        const f32x2 p0 = __builtin_amdgcn_cvt_pk_f32_fp8(q.x, false);
+        const f32x2 p1 = __builtin_amdgcn_cvt_pk_f32_fp8(q.x, true);
+        const f32x2 p2 = __builtin_amdgcn_cvt_pk_f32_fp8(q.y, false);
+        const f32x2 p3 = __builtin_amdgcn_cvt_pk_f32_fp8(q.y, true);
+        v[0] = f2bf(p0[0] * sc); v[1] = f2bf(p0[1] * sc);
+        v[2] = f2bf(p1[0] * sc); v[3] = f2bf(p1[1] * sc);
+        v[4] = f2bf(p2[0] * sc); v[5] = f2bf(p2[1] * sc);
+        v[6] = f2bf(p3[0] * sc); v[7] = f2bf(p3[1] * sc);
+      } else {
+        v = *reinterpret_cast<const bf16x8*>(
+            wbase + (long)(n0 + r) * H + k0 + c);
+      }
       *reinterpret_cast<bf16x8*>(&ws[r][c]) = v;
     }
     __syncthreads();
@@ -696,9 +730,22 @@ void moe_grouped_gemm128(torch::Tensor out, torch::Tensor x, torch::Tensor w,
   dim3 grid(G, N / G2_BN), block(512);
   hipLaunchKernelGGL((moe_grouped_gemm128_kernel<G2_BM, G2_BN>), grid, block, 0, s,
                      (short*)out.data_ptr(), (const short*)x.data_ptr(),
-                     (const short*)w.data_ptr(), pair_token.data_ptr<int>(),
-                     tile_desc.data_ptr<int>(), H, N);
+                     (const void*)w.data_ptr(), (const float*)nullptr,
+                     pair_token.data_ptr<int>(), tile_desc.data_ptr<int>(),
+                     H, N);
   HIP_CHECK_KERNEL();
+}
+
+// launch of the e4m3 instantiation; every argument is checked by its caller,
+// moe_grouped_gemm128_fp8 in moe_fp8.hip (N, H multiples of 128, G >= 1)
+void moe_grouped_gemm128_fp8_launch(short* out, const short* x,
+                                    const uint8_t* w_q, const float* w_s,
+                                    const int* pair_token, const int* tile_desc,
+                                    int G, int H, int N, hipStream_t s) {
+  dim3 grid(G, N / G2_BN), block(512);
+  hipLaunchKernelGGL(
+      (moe_grouped_gemm128_kernel<G2_BM, G2_BN, G2_BK, true>), grid, block, 0,
+      s, out, x, (const void*)w_q, w_s, pair_token, tile_desc, H, N);
 }
 
 // gather-combine: out[t] = Σ_k w[t,k] * z[inv_order[t*K+k]] — an atomicAdd

@@ -522,3 +522,50 @@ void moe_grouped_gemm_skinny_fp8(torch::Tensor out, torch::Tensor x,
                  (int)G, (int)K, (int)N, f32out, s);
   HIP_CHECK_KERNEL();
 }
+
+// ------------------------------------------------ prefill grouped GEMM, fp8 w
+// BM=128 tiles (tile_desc from moe_build_desc with bm=128). The kernel is the
+// W8 instantiation of moe_grouped_gemm128_kernel in moe.hip, which shares the
+// bf16 kernel's MFMA loop. Its numeric contract is NOT the one at the top of
+// this file: the scale is applied to the weight, bf16_rne(f32(q) * s), while
+// the tile is staged, so the result equals moe_grouped_gemm128 on
+// dequantize_fp8_block(w_q, w_s).to(bf16) bit for bit.
+void moe_grouped_gemm128_fp8_launch(short* out, const short* x,
+                                    const uint8_t* w_q, const float* w_s,
+                                    const int* pair_token, const int* tile_desc,
+                                    int G, int H, int N, hipStream_t s);
+
+void moe_grouped_gemm128_fp8(torch::Tensor out, torch::Tensor x,
+                             torch::Tensor w_q, torch::Tensor w_s,
+                             torch::Tensor pair_token,
+                             torch::Tensor tile_desc) {
+  fp8_check_weights(w_q, w_s, "moe_grouped_gemm128_fp8");
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2,
+              "moe_grouped_gemm128_fp8: x is [T, K], out is [P, N]");
+  const int64_t K = x.size(1), N = w_q.size(1);
+  TORCH_CHECK(w_q.size(2) == K && out.size(1) == N,
+              "moe_grouped_gemm128_fp8: shape mismatch");
+  TORCH_CHECK(x.is_cuda() && out.is_cuda() && x.dtype() == torch::kBFloat16
+              && out.dtype() == torch::kBFloat16,
+              "moe_grouped_gemm128_fp8: x and out must be bf16 on the GPU");
+  TORCH_CHECK(x.is_contiguous() && out.is_contiguous(),
+              "moe_grouped_gemm128_fp8: x and out must be contiguous");
+  TORCH_CHECK(pair_token.is_cuda() && pair_token.dtype() == torch::kInt32
+              && pair_token.is_contiguous()
+              && pair_token.numel() == out.size(0),
+              "pair_token is int32 with one entry per out row");
+  TORCH_CHECK(tile_desc.is_cuda() && tile_desc.dtype() == torch::kInt32
+              && tile_desc.dim() == 2 && tile_desc.is_contiguous()
+              && tile_desc.size(1) == 3,
+              "tile_desc is contiguous int32 [G, 3]");
+  const int64_t G = tile_desc.size(0);
+  TORCH_CHECK(G >= 1 && G <= 0x7fffffffL && N / 64 <= 65535
+              && K <= 0x7fffffffL);
+  hipStream_t s = c10::hip::getCurrentHIPStream();
+  moe_grouped_gemm128_fp8_launch(
+      (short*)out.data_ptr(), (const short*)x.data_ptr(),
+      (const uint8_t*)w_q.data_ptr(), w_s.data_ptr<float>(),
+      pair_token.data_ptr<int>(), tile_desc.data_ptr<int>(), (int)G, (int)K,
+      (int)N, s);
+  HIP_CHECK_KERNEL();
+}

@@ -71,7 +71,8 @@ class _DecodeGraph:
         def run_step():
             logits = model.forward(self.tok_in, self.seq_in, self.pos_in,
                                    cache.block_table, cache.kcaches,
-                                   cache.vcaches)
+                                   cache.vcaches, kscales=cache.kscales,
+                                   vscales=cache.vscales)
             toks = torch.empty(bucket, dtype=torch.int32, device=dev)
             C.sample_rows(toks, logits, self.temperature, self.top_p,
                           self.top_k, self.seeds, self.pos_in, self.rep,
@@ -172,7 +173,8 @@ class _PrefillGraph:
             return model.forward(self.tok, self.seq, self.pos,
                                  cache.block_table, cache.kcaches,
                                  cache.vcaches, logits_rows=self.rows,
-                                 qtile_desc=self.qtiles)
+                                 qtile_desc=self.qtiles,
+                                 kscales=cache.kscales, vscales=cache.vscales)
 
         # warmup on the CURRENT stream, not a side stream: the canonical
         # side-stream warmup HANGS on the 30b config at tb=512 (bisected in

@@ -9,22 +9,47 @@ from __future__ import annotations
 import torch
 
 BLOCK_SIZE = 16
+KV_DTYPES = ("bf16", "fp8")
+
+
+def _check_kv_dtype(kv_dtype: str) -> None:
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, "
+                         f"got {kv_dtype!r}")
 
 
 class PagedKVCache:
     def __init__(self, num_layers: int, num_kv_heads: int, head_dim: int,
                  num_blocks: int, max_seqs: int, max_blocks_per_seq: int,
-                 device: torch.device):
+                 device: torch.device, kv_dtype: str = "bf16"):
+        """kv_dtype "bf16": K and V rows as bf16. "fp8": rows as e4m3fn
+        bytes plus one f32 scale per row (kscales/vscales, [num_blocks, Hk,
+        16] per layer; ops.reference.quantize_kv_rows is the format). A row
+        and its scale are written together when its token is, so appending
+        and rolling back overwrite whole rows and nothing is requantised."""
+        _check_kv_dtype(kv_dtype)
+        self.kv_dtype = kv_dtype
         self.block_size = BLOCK_SIZE
         self.num_blocks = num_blocks
         self.max_seqs = max_seqs
         self.max_blocks_per_seq = max_blocks_per_seq
-        self.kcaches = [torch.zeros(num_blocks, num_kv_heads, BLOCK_SIZE, head_dim,
-                                    dtype=torch.bfloat16, device=device)
-                        for _ in range(num_layers)]
-        self.vcaches = [torch.zeros(num_blocks, num_kv_heads, BLOCK_SIZE, head_dim,
-                                    dtype=torch.bfloat16, device=device)
-                        for _ in range(num_layers)]
+        fp8 = kv_dtype == "fp8"
+        row_dtype = torch.float8_e4m3fn if fp8 else torch.bfloat16
+
+        def rows():
+            return [torch.zeros(num_blocks, num_kv_heads, BLOCK_SIZE, head_dim,
+                                dtype=row_dtype, device=device)
+                    for _ in range(num_layers)]
+
+        def scales():
+            return [torch.ones(num_blocks, num_kv_heads, BLOCK_SIZE,
+                               dtype=torch.float32, device=device)
+                    for _ in range(num_layers)]
+
+        self.kcaches, self.vcaches = rows(), rows()
+        # None in bf16 mode: the ops take it as "no scales"
+        self.kscales = scales() if fp8 else None
+        self.vscales = scales() if fp8 else None
         self.block_table = torch.zeros(max_seqs, max_blocks_per_seq,
                                        dtype=torch.int32, device=device)
         self._bt_host = [[0] * max_blocks_per_seq for _ in range(max_seqs)]
@@ -34,8 +59,12 @@ class PagedKVCache:
         self.seq_nblocks: dict[int, int] = {}
 
     @staticmethod
-    def bytes_per_block(num_layers: int, num_kv_heads: int, head_dim: int) -> int:
-        return num_layers * 2 * num_kv_heads * BLOCK_SIZE * head_dim * 2
+    def bytes_per_block(num_layers: int, num_kv_heads: int, head_dim: int,
+                        kv_dtype: str = "bf16") -> int:
+        _check_kv_dtype(kv_dtype)
+        # per cached row: bf16 values, or e4m3 bytes and the f32 row scale
+        row_bytes = head_dim + 4 if kv_dtype == "fp8" else head_dim * 2
+        return num_layers * 2 * num_kv_heads * BLOCK_SIZE * row_bytes
 
     def alloc_seq(self) -> int:
         if not self.free_slots:

@@ -73,6 +73,15 @@ def expert_dtype_from_env(environ=os.environ) -> str:
     return v
 
 
+def kv_dtype_from_env(environ=os.environ) -> str:
+    """KV-cache storage from ROOMAMD_KV_DTYPE: unset, empty or "bf16" is the
+    default, "fp8" the e4m3 rows with one f32 scale per row."""
+    v = environ.get("ROOMAMD_KV_DTYPE", "").strip() or "bf16"
+    if v not in ("bf16", "fp8"):
+        raise ValueError(f"ROOMAMD_KV_DTYPE must be bf16 or fp8, got {v!r}")
+    return v
+
+
 def expert_image_from_env(environ=os.environ) -> bool:
     """Whether an fp8 engine keeps the bf16 image of its expert weights, from
     ROOMAMD_EXPERT_IMAGE: unset, empty or "1" keeps it (prefill reads the
@@ -108,6 +117,7 @@ class LocalEngine:
         # expert-weight storage, read here once (docs/CONFIG.md)
         self.expert_dtype = expert_dtype_from_env()
         self.expert_image = expert_image_from_env()
+        self.kv_dtype = kv_dtype_from_env()
         if not self.expert_image and self.expert_dtype != "fp8":
             raise ValueError(
                 "ROOMAMD_EXPERT_IMAGE=0 needs ROOMAMD_EXPERT_DTYPE=fp8: with "
@@ -120,7 +130,7 @@ class LocalEngine:
         self.load_seconds = time.time() - t0
 
         bpb = PagedKVCache.bytes_per_block(cfg.num_layers, cfg.num_kv_heads,
-                                           cfg.head_dim)
+                                           cfg.head_dim, self.kv_dtype)
         if kv_gb is None:
             free_b, _total = torch.cuda.mem_get_info(self.device)
             kv_bytes = max(int(free_b - 8e9), 2 << 30)  # leave 8 GB headroom
@@ -130,7 +140,7 @@ class LocalEngine:
         num_blocks = min(kv_bytes // bpb, max_seqs * max_blocks_per_seq + 1)
         self.cache = PagedKVCache(cfg.num_layers, cfg.num_kv_heads, cfg.head_dim,
                                   int(num_blocks), max_seqs, max_blocks_per_seq,
-                                  self.device)
+                                  self.device, kv_dtype=self.kv_dtype)
         # pad slot for hipGraph batch padding (one scrap block absorbs the
         # dummy lanes' KV writes)
         self.pad_slot = self.cache.alloc_seq()
@@ -387,7 +397,8 @@ class LocalEngine:
             logits = self.model.forward(
                 tokens_t, seq_t, pos_t, self.cache.block_table,
                 self.cache.kcaches, self.cache.vcaches, logits_rows=rows_t,
-                qtile_desc=qtiles)
+                qtile_desc=qtiles, kscales=self.cache.kscales,
+                vscales=self.cache.vscales)
         self.stats["prefill_enq_time"] += time.time() - t0
         self.stats["prefill_tokens"] += n
         if sampled:
@@ -441,7 +452,9 @@ class LocalEngine:
                 r.pos += 1
             logits = self.model.forward(tokens_t, seq_t, pos_t,
                                         self.cache.block_table,
-                                        self.cache.kcaches, self.cache.vcaches)
+                                        self.cache.kcaches, self.cache.vcaches,
+                                        kscales=self.cache.kscales,
+                                        vscales=self.cache.vscales)
             rows = [self._sample(reqs, logits, positions)]
         self._accept(reqs, rows, advance_pos=plan.use_graph)
         self.stats["decode_steps"] += plan.steps

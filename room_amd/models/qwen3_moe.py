@@ -249,9 +249,13 @@ class Qwen3MoEModel:
                 q_pos: torch.Tensor, block_table: torch.Tensor,
                 kcaches: list[torch.Tensor], vcaches: list[torch.Tensor],
                 logits_rows: torch.Tensor | None = None,
-                qtile_desc: torch.Tensor | None = None) -> torch.Tensor:
+                qtile_desc: torch.Tensor | None = None,
+                kscales: list[torch.Tensor] | None = None,
+                vscales: list[torch.Tensor] | None = None) -> torch.Tensor:
         """tokens/seq_ids/q_pos: [T] on device. kcaches/vcaches: one pair per
         layer. logits_rows: row indices to compute logits for (default: all).
+        kscales/vscales: the per-row scales of an fp8 KV cache, one pair per
+        layer (PagedKVCache(kv_dtype="fp8")); None with bf16 caches.
         Returns fp32 logits [R, vocab]."""
         cfg = self.cfg
         T = tokens.numel()
@@ -271,6 +275,8 @@ class Qwen3MoEModel:
         st = _Step(seq_ids=seq_ids, q_pos=q_pos, block_table=block_table,
                    qtile_desc=qtile_desc,
                    hbuf=torch.empty_like(x))       # normed activations
+        if (kscales is None) != (vscales is None):
+            raise ValueError("kscales and vscales go together")
         moe_out = None                             # pending delta for fused add
         # layer-invariant MoE pair/token indices (was re-built 48×/step: an
         # arange+repeat_interleave kernel pair per layer in the decode graph)
@@ -304,15 +310,22 @@ class Qwen3MoEModel:
             st.moe_out = torch.empty(T, cfg.hidden_size, **bf)
 
         for li, layer in enumerate(self.layers):
+            # fp8 KV cache: the layer's row scales ride along with its caches
+            # (no extra argument in bf16 mode)
+            sc = ({} if kscales is None
+                  else dict(kscale=kscales[li], vscale=vscales[li]))
             if decode:
                 x, x_alt, moe_out = self._decode_layer(
-                    layer, kcaches[li], vcaches[li], st, x, x_alt, moe_out)
+                    layer, kcaches[li], vcaches[li], st, x, x_alt, moe_out,
+                    **sc)
             elif wide:
                 moe_out = self._wide_layer(
-                    layer, kcaches[li], vcaches[li], st, x, moe_out)
+                    layer, kcaches[li], vcaches[li], st, x, moe_out,
+                    **sc)
             else:
                 moe_out = self._prefill_layer(
-                    layer, kcaches[li], vcaches[li], st, x, moe_out)
+                    layer, kcaches[li], vcaches[li], st, x, moe_out,
+                    **sc)
 
         # final residual add + norm; skip lm_head entirely for logits-free
         # prefill chunks (an empty logits_rows means "no sampling this chunk")
@@ -340,7 +353,9 @@ class Qwen3MoEModel:
 
     def _decode_layer(self, layer: Qwen3MoELayer, kcache: torch.Tensor,
                       vcache: torch.Tensor, st: "_Step", x: torch.Tensor,
-                      x_alt: torch.Tensor, moe_out: torch.Tensor | None):
+                      x_alt: torch.Tensor, moe_out: torch.Tensor | None,
+                      kscale: torch.Tensor | None = None,
+                      vscale: torch.Tensor | None = None):
         """One layer at T ≤ 8: every projection on the hand-written GEMVs,
         split-KV attention, pair-GEMV MoE. Returns (x, x_alt, moe_out); the
         residual ping-pongs between x and x_alt at T ≤ 2."""
@@ -376,12 +391,13 @@ class Qwen3MoEModel:
         ops.qk_rope_write_kv(qkv, cfg.num_q_heads, kcache, vcache,
                              layer.q_norm_w, layer.k_norm_w, self.cos_t,
                              self.sin_t, st.block_table, st.seq_ids, st.q_pos,
-                             cfg.rms_eps)
+                             cfg.rms_eps, kscale, vscale)
         attn = torch.empty(T, cfg.num_q_heads, cfg.head_dim,
                            dtype=torch.bfloat16, device=x.device)
         ops.paged_attention_split(attn, q, kcache, vcache, st.block_table,
                                   st.seq_ids, st.q_pos, st.part, st.part_ml,
-                                  self.scale, splits=self.attn_splits)
+                                  self.scale, splits=self.attn_splits,
+                                  k_scale=kscale, v_scale=vscale)
         # O projection with the residual add in its epilogue (x updated in
         # place), then the post-attention norm inside the router GEMV, which
         # also leaves the normed rows in hbuf for the MoE: no norm launch
@@ -394,7 +410,9 @@ class Qwen3MoEModel:
 
     def _wide_layer(self, layer: Qwen3MoELayer, kcache: torch.Tensor,
                     vcache: torch.Tensor, st: "_Step", x: torch.Tensor,
-                    moe_out: torch.Tensor | None) -> torch.Tensor:
+                    moe_out: torch.Tensor | None,
+                    kscale: torch.Tensor | None = None,
+                    vscale: torch.Tensor | None = None) -> torch.Tensor:
         """One layer at 9 ≤ T ≤ 64 (a decode batch): every projection and
         both MoE GEMMs on the skinny MFMA GEMM, split-KV attention per row,
         expert-sorted MoE with the gather combine. No hipBLASLt (capture-
@@ -415,10 +433,11 @@ class Qwen3MoEModel:
         ops.qk_rope_write_kv(qkv, cfg.num_q_heads, kcache, vcache,
                              layer.q_norm_w, layer.k_norm_w, self.cos_t,
                              self.sin_t, st.block_table, st.seq_ids, st.q_pos,
-                             cfg.rms_eps)
+                             cfg.rms_eps, kscale, vscale)
         ops.paged_attention_split(st.attn, q, kcache, vcache, st.block_table,
                                   st.seq_ids, st.q_pos, st.part, st.part_ml,
-                                  self.scale, splits=self.attn_splits)
+                                  self.scale, splits=self.attn_splits,
+                                  k_scale=kscale, v_scale=vscale)
         ops.skinny_gemm(st.obuf, st.attn.view(T, qdim), layer.wo)
         # --- MoE block
         ops.fused_add_rmsnorm(hbuf, x, st.obuf, layer.post_attn_norm_w,
@@ -473,7 +492,9 @@ class Qwen3MoEModel:
 
     def _prefill_layer(self, layer: Qwen3MoELayer, kcache: torch.Tensor,
                        vcache: torch.Tensor, st: "_Step", x: torch.Tensor,
-                       moe_out: torch.Tensor | None) -> torch.Tensor:
+                       moe_out: torch.Tensor | None,
+                       kscale: torch.Tensor | None = None,
+                       vscale: torch.Tensor | None = None) -> torch.Tensor:
         """One layer at T > 8: dense projections through _dense, MFMA flash
         prefill (or the unified paged kernel without q-tile descriptors),
         grouped-GEMM MoE. x is updated in place; returns moe_out."""
@@ -492,16 +513,18 @@ class Qwen3MoEModel:
         ops.qk_rope_write_kv(qkv, cfg.num_q_heads, kcache, vcache,
                              layer.q_norm_w, layer.k_norm_w, self.cos_t,
                              self.sin_t, st.block_table, st.seq_ids, st.q_pos,
-                             cfg.rms_eps)
+                             cfg.rms_eps, kscale, vscale)
         attn = torch.empty(T, cfg.num_q_heads, cfg.head_dim,
                            dtype=torch.bfloat16, device=x.device)
         if st.qtile_desc is not None:
             ops.flash_prefill(attn, q, kcache, vcache, st.block_table,
-                              st.seq_ids, st.q_pos, st.qtile_desc, self.scale)
+                              st.seq_ids, st.q_pos, st.qtile_desc, self.scale,
+                              kscale, vscale)
             o = self._dense(attn.reshape(T, qdim), layer.wo)
         else:
             ops.paged_attention(attn, q, kcache, vcache, st.block_table,
-                                st.seq_ids, st.q_pos, self.scale)
+                                st.seq_ids, st.q_pos, self.scale,
+                                kscale, vscale)
             o = F.linear(attn.reshape(T, qdim), layer.wo)
         # --- MoE block
         ops.fused_add_rmsnorm(hbuf, x, o, layer.post_attn_norm_w, cfg.rms_eps)

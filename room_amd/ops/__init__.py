@@ -56,12 +56,21 @@ def qk_rope_write_kv(qkv: torch.Tensor, n_qheads: int,
                      q_w: torch.Tensor, k_w: torch.Tensor,
                      cos_t: torch.Tensor, sin_t: torch.Tensor,
                      block_table: torch.Tensor, seq_ids: torch.Tensor,
-                     positions: torch.Tensor, eps: float = 1e-6) -> None:
+                     positions: torch.Tensor, eps: float = 1e-6,
+                     k_scale: torch.Tensor | None = None,
+                     v_scale: torch.Tensor | None = None) -> None:
     """Fused per-head QK RMSNorm + RoPE + paged KV scatter, operating directly
-    on the packed [T, (Hq+2Hk)*D] projection output (no q/k/v copies)."""
+    on the packed [T, (Hq+2Hk)*D] projection output (no q/k/v copies).
+
+    fp8 KV cache: with float8_e4m3fn caches, k_scale and v_scale
+    [NB, Hk, 16] f32 are required; every written row gets the bytes and the
+    scale of reference.quantize_kv_rows of the row the bf16 form stores, and
+    Q gets the same bits. (The same two arguments on the three attention ops
+    below: their output is bit-equal to the bf16 op on the cache's image,
+    dequantize_kv_rows(...).to(bf16).)"""
     _require().qk_rope_write_kv(qkv, kcache, vcache, q_w, k_w, cos_t,
                                 sin_t, block_table, seq_ids, positions,
-                                n_qheads, eps)
+                                n_qheads, eps, k_scale, v_scale)
 
 
 def silu_mul(out: torch.Tensor, gateup: torch.Tensor) -> torch.Tensor:
@@ -72,9 +81,10 @@ def silu_mul(out: torch.Tensor, gateup: torch.Tensor) -> torch.Tensor:
 def paged_attention(out: torch.Tensor, q: torch.Tensor, kcache: torch.Tensor,
                     vcache: torch.Tensor, block_table: torch.Tensor,
                     seq_ids: torch.Tensor, q_pos: torch.Tensor,
-                    scale: float) -> torch.Tensor:
+                    scale: float, k_scale: torch.Tensor | None = None,
+                    v_scale: torch.Tensor | None = None) -> torch.Tensor:
     _require().paged_attention(out, q, kcache, vcache, block_table, seq_ids,
-                               q_pos, scale)
+                               q_pos, scale, k_scale, v_scale)
     return out
 
 
@@ -95,13 +105,15 @@ def paged_attention_split(out: torch.Tensor, q: torch.Tensor, kcache: torch.Tens
                           vcache: torch.Tensor, block_table: torch.Tensor,
                           seq_ids: torch.Tensor, q_pos: torch.Tensor,
                           part: torch.Tensor, part_ml: torch.Tensor,
-                          scale: float, splits: int = 32) -> torch.Tensor:
+                          scale: float, splits: int = 32,
+                          k_scale: torch.Tensor | None = None,
+                          v_scale: torch.Tensor | None = None) -> torch.Tensor:
     """Split-KV flash-decode: part [T, Hq, NSPLITS_MAX, 128] f32, part_ml
     [.., 2]; `splits` (32 short / 64 long contexts) sets the launch grid —
     shorter per-WG chunk chains win once the serial span passes ~8k."""
     _require().paged_attention_split(out, q, kcache, vcache, block_table,
                                      seq_ids, q_pos, part, part_ml, scale,
-                                     splits)
+                                     splits, k_scale, v_scale)
     return out
 
 
@@ -123,13 +135,15 @@ def gemv_residual(r: torch.Tensor, x: torch.Tensor, w: torch.Tensor
 def flash_prefill(out: torch.Tensor, q: torch.Tensor, kcache: torch.Tensor,
                   vcache: torch.Tensor, block_table: torch.Tensor,
                   seq_ids: torch.Tensor, q_pos: torch.Tensor,
-                  tile_desc: torch.Tensor, scale: float) -> torch.Tensor:
+                  tile_desc: torch.Tensor, scale: float,
+                  k_scale: torch.Tensor | None = None,
+                  v_scale: torch.Tensor | None = None) -> torch.Tensor:
     """MFMA flash prefill; tile_desc [G,2] = (row0, n_tokens≤32), one sequence
     per tile (build with build_qtile_desc). q may be a row-strided view of
     the packed qkv; out, the caches, the block table and the int32 vectors
     must be contiguous (checked by the wrapper)."""
     _require().flash_prefill(out, q, kcache, vcache, block_table, seq_ids,
-                             q_pos, tile_desc, scale)
+                             q_pos, tile_desc, scale, k_scale, v_scale)
     return out
 
 

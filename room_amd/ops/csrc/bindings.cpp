@@ -12,11 +12,15 @@ void qk_rope_write_kv(torch::Tensor qkv, torch::Tensor kcache,
                       torch::Tensor vcache, torch::Tensor q_w, torch::Tensor k_w,
                       torch::Tensor cos_t, torch::Tensor sin_t,
                       torch::Tensor block_table, torch::Tensor seq_ids,
-                      torch::Tensor positions, int64_t n_qheads, double eps);
+                      torch::Tensor positions, int64_t n_qheads, double eps,
+                      c10::optional<torch::Tensor> k_scale,
+                      c10::optional<torch::Tensor> v_scale);
 void silu_mul(torch::Tensor out, torch::Tensor gateup);
 void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
                      torch::Tensor vcache, torch::Tensor block_table,
-                     torch::Tensor seq_ids, torch::Tensor q_pos, double scale);
+                     torch::Tensor seq_ids, torch::Tensor q_pos, double scale,
+                     c10::optional<torch::Tensor> k_scale,
+                     c10::optional<torch::Tensor> v_scale);
 void write_kv(torch::Tensor kcache, torch::Tensor vcache, torch::Tensor k,
               torch::Tensor v, torch::Tensor block_table, torch::Tensor seq_ids,
               torch::Tensor q_pos);
@@ -62,13 +66,17 @@ void paged_attention_split(torch::Tensor out, torch::Tensor q,
                            torch::Tensor block_table, torch::Tensor seq_ids,
                            torch::Tensor q_pos, torch::Tensor part,
                            torch::Tensor part_ml, double scale,
-                           int64_t splits);
+                           int64_t splits,
+                           c10::optional<torch::Tensor> k_scale,
+                           c10::optional<torch::Tensor> v_scale);
 int64_t attn_nsplits();
 int64_t flash_prefill_qtile();
 void flash_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
                    torch::Tensor vcache, torch::Tensor block_table,
                    torch::Tensor seq_ids, torch::Tensor q_pos,
-                   torch::Tensor tile_desc, double scale);
+                   torch::Tensor tile_desc, double scale,
+                   c10::optional<torch::Tensor> k_scale,
+                   c10::optional<torch::Tensor> v_scale);
 void gemv(torch::Tensor y, torch::Tensor x, torch::Tensor w);
 void gemv_residual(torch::Tensor r, torch::Tensor x, torch::Tensor w);
 void gemv_addnorm(torch::Tensor y, torch::Tensor x, torch::Tensor delta,

@@ -19,6 +19,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
+#include "kv_fp8.h"
 
 #define FP_BS 16          // paged KV block size
 #define FP_QTOK 32        // q tokens per tile (2 MFMA row-blocks)
@@ -29,17 +30,26 @@
 
 typedef __attribute__((ext_vector_type(4))) float fpfrag_t;
 
+// F8: the caches hold e4m3 bytes and kscale/vscale [NB, Hk, 16] one f32 per
+// row (kv_fp8.h). Only the staging step differs: a thread loads 8 B of K,
+// 8 B of V and the row's two scales and writes the image's bf16 values, so
+// k_s and vt_s hold what the bf16 form stages.
+template <bool F8>
 __global__ __launch_bounds__(512, 1)
 void flash_prefill_kernel(short* __restrict__ out,         // [T, Hq, D]
                           const short* __restrict__ q,      // [T, Hq, D]
-                          const short* __restrict__ kcache, // [NB, Hk, 16, D]
-                          const short* __restrict__ vcache,
+                          const std::conditional_t<F8, uint8_t, short>*
+                              __restrict__ kcache,          // [NB, Hk, 16, D]
+                          const std::conditional_t<F8, uint8_t, short>*
+                              __restrict__ vcache,
                           const int* __restrict__ block_table,
                           const int* __restrict__ seq_ids,
                           const int* __restrict__ q_pos,
                           const int* __restrict__ tile_desc,  // [G, 2]: row0, n
                           int n_kvheads, int max_blocks, int q_row_stride,
-                          float scale) {
+                          float scale,
+                          const float* __restrict__ kscale,
+                          const float* __restrict__ vscale) {
   const int g = blockIdx.x;
   const int hk = blockIdx.y;
   const int row0 = tile_desc[g * 2 + 0];
@@ -115,8 +125,16 @@ void flash_prefill_kernel(short* __restrict__ out,         // [T, Hq, D]
         const int blk = btab[pos / FP_BS];
         const long off = (long)blk * kv_stride_block
                          + ((long)hk * FP_BS + (pos % FP_BS)) * FP_D + d8;
-        kv = *reinterpret_cast<const bf16x8*>(kcache + off);
-        vv = *reinterpret_cast<const bf16x8*>(vcache + off);
+        if constexpr (F8) {
+          const long soff = ((long)blk * n_kvheads + hk) * FP_BS + pos % FP_BS;
+          const kv_u32x2 kq = *reinterpret_cast<const kv_u32x2*>(kcache + off);
+          const kv_u32x2 vq = *reinterpret_cast<const kv_u32x2*>(vcache + off);
+          kv = __builtin_bit_cast(bf16x8, kv_fp8x8_to_bf16(kq, kscale[soff]));
+          vv = __builtin_bit_cast(bf16x8, kv_fp8x8_to_bf16(vq, vscale[soff]));
+        } else {
+          kv = *reinterpret_cast<const bf16x8*>(kcache + off);
+          vv = *reinterpret_cast<const bf16x8*>(vcache + off);
+        }
       }
       *reinterpret_cast<bf16x8*>(&k_s[pos_l][d8]) = kv;
       #pragma unroll
@@ -247,7 +265,11 @@ void flash_prefill_kernel(short* __restrict__ out,         // [T, Hq, D]
 void flash_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
                    torch::Tensor vcache, torch::Tensor block_table,
                    torch::Tensor seq_ids, torch::Tensor q_pos,
-                   torch::Tensor tile_desc, double scale) {
+                   torch::Tensor tile_desc, double scale,
+                   c10::optional<torch::Tensor> k_scale,
+                   c10::optional<torch::Tensor> v_scale) {
+  const bool fp8 = kv_fp8_check("flash_prefill", kcache, vcache, k_scale,
+                                v_scale);
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16);
   TORCH_CHECK(q.dim() == 3 && q.size(-1) == FP_D, "q is [T, Hq, 128]");
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == FP_D);  // strided row-views OK
@@ -256,14 +278,6 @@ void flash_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
   TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kBFloat16 &&
               out.is_contiguous() && out.sizes() == q.sizes(),
               "out must be contiguous bf16 shaped like q");
-  TORCH_CHECK(kcache.is_cuda() && vcache.is_cuda() &&
-              kcache.dtype() == torch::kBFloat16 &&
-              vcache.dtype() == torch::kBFloat16 &&
-              kcache.is_contiguous() && vcache.is_contiguous(),
-              "caches must be contiguous bf16");
-  TORCH_CHECK(kcache.dim() == 4 && kcache.size(2) == FP_BS &&
-              kcache.size(3) == FP_D && vcache.sizes() == kcache.sizes(),
-              "caches are [NB, Hk, 16, 128] and equally shaped");
   TORCH_CHECK(tile_desc.is_cuda() && tile_desc.dtype() == torch::kInt32 &&
               tile_desc.dim() == 2 && tile_desc.size(1) == 2 &&
               tile_desc.is_contiguous(), "tile_desc is contiguous int32 [G, 2]");
@@ -282,13 +296,24 @@ void flash_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
   const int max_blocks = block_table.size(1);
   dim3 grid(G, n_kvheads), block(512);
   hipStream_t s = c10::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(flash_prefill_kernel, grid, block, 0, s,
-                     (short*)out.data_ptr(), (const short*)q.data_ptr(),
-                     (const short*)kcache.data_ptr(),
-                     (const short*)vcache.data_ptr(),
-                     block_table.data_ptr<int>(), seq_ids.data_ptr<int>(),
-                     q_pos.data_ptr<int>(), tile_desc.data_ptr<int>(),
-                     n_kvheads, max_blocks, (int)q.stride(0), (float)scale);
+  if (fp8)
+    hipLaunchKernelGGL(flash_prefill_kernel<true>, grid, block, 0, s,
+                       (short*)out.data_ptr(), (const short*)q.data_ptr(),
+                       (const uint8_t*)kcache.data_ptr(),
+                       (const uint8_t*)vcache.data_ptr(),
+                       block_table.data_ptr<int>(), seq_ids.data_ptr<int>(),
+                       q_pos.data_ptr<int>(), tile_desc.data_ptr<int>(),
+                       n_kvheads, max_blocks, (int)q.stride(0), (float)scale,
+                       k_scale->data_ptr<float>(), v_scale->data_ptr<float>());
+  else
+    hipLaunchKernelGGL(flash_prefill_kernel<false>, grid, block, 0, s,
+                       (short*)out.data_ptr(), (const short*)q.data_ptr(),
+                       (const short*)kcache.data_ptr(),
+                       (const short*)vcache.data_ptr(),
+                       block_table.data_ptr<int>(), seq_ids.data_ptr<int>(),
+                       q_pos.data_ptr<int>(), tile_desc.data_ptr<int>(),
+                       n_kvheads, max_blocks, (int)q.stride(0), (float)scale,
+                       (const float*)nullptr, (const float*)nullptr);
   HIP_CHECK_KERNEL();
 }
 

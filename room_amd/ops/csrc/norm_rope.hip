@@ -8,6 +8,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
+#include "kv_fp8.h"
 
 // ---------------------------------------------------------------- rmsnorm
 // y = x / rms(x) * w.   rows × cols, cols % 8 == 0, cols <= 8192.
@@ -241,9 +242,17 @@ void silu_mul(torch::Tensor out, torch::Tensor gateup) {
 // qkv is the packed projection output [T, (Hq+2Hk)*D]; row_stride lets the
 // kernel read q/k/v in place (no .contiguous() copies — profiled at 0.67
 // ms/decode-step). Rotated Q is written back into the qkv buffer.
+//
+// F8 (fp8 KV cache, kv_fp8.h): kcache/vcache hold e4m3 bytes and kscale/vscale
+// [NB,Hk,16] one f32 per row. A K or V workgroup takes the bf16 row the plain
+// form stores, then block amax -> scale -> one byte per thread; Q workgroups
+// are the same code.
+template <bool F8>
 __global__ void qk_rope_write_kv_kernel(short* __restrict__ qkv,
-                                        short* __restrict__ kcache,  // [NB,Hk,16,D]
-                                        short* __restrict__ vcache,
+                                        std::conditional_t<F8, uint8_t, short>*
+                                            __restrict__ kcache,  // [NB,Hk,16,D]
+                                        std::conditional_t<F8, uint8_t, short>*
+                                            __restrict__ vcache,
                                         const short* __restrict__ q_w,
                                         const short* __restrict__ k_w,
                                         const float* __restrict__ cos_t,
@@ -253,7 +262,9 @@ __global__ void qk_rope_write_kv_kernel(short* __restrict__ qkv,
                                         const int* __restrict__ pos,
                                         int n_qheads, int n_kvheads,
                                         int head_dim, int max_blocks,
-                                        int row_stride, float eps) {
+                                        int row_stride, float eps,
+                                        float* __restrict__ kscale,
+                                        float* __restrict__ vscale) {
   const int t = blockIdx.x;
   const int h = blockIdx.y;
   const int i = threadIdx.x;
@@ -265,8 +276,15 @@ __global__ void qk_rope_write_kv_kernel(short* __restrict__ qkv,
   const long row = (long)t * row_stride;
   if (h >= n_qheads + n_kvheads) {        // V scatter (no rope)
     const int hv = h - n_qheads - n_kvheads;
-    vcache[cache_off + (long)hv * 16 * head_dim + i] =
-        qkv[row + (long)(n_qheads + n_kvheads + hv) * head_dim + i];
+    const short v = qkv[row + (long)(n_qheads + n_kvheads + hv) * head_dim + i];
+    if constexpr (F8) {
+      __shared__ uint32_t amax_v[2];
+      kv_fp8_store_row(vcache + cache_off + (long)hv * 16 * head_dim,
+                       vscale + ((long)blk * n_kvheads + hv) * 16 + p % 16,
+                       v, amax_v);
+    } else {
+      vcache[cache_off + (long)hv * 16 * head_dim + i] = v;
+    }
     return;
   }
 
@@ -295,7 +313,14 @@ __global__ void qk_rope_write_kv_kernel(short* __restrict__ qkv,
     qkv[row + (long)h * head_dim + i] = f2bf(out);
   } else {
     const int hk = h - n_qheads;
-    kcache[cache_off + (long)hk * 16 * head_dim + i] = f2bf(out);
+    if constexpr (F8) {
+      __shared__ uint32_t amax_k[2];
+      kv_fp8_store_row(kcache + cache_off + (long)hk * 16 * head_dim,
+                       kscale + ((long)blk * n_kvheads + hk) * 16 + p % 16,
+                       f2bf(out), amax_k);
+    } else {
+      kcache[cache_off + (long)hk * 16 * head_dim + i] = f2bf(out);
+    }
   }
 }
 
@@ -303,7 +328,11 @@ void qk_rope_write_kv(torch::Tensor qkv, torch::Tensor kcache,
                       torch::Tensor vcache, torch::Tensor q_w, torch::Tensor k_w,
                       torch::Tensor cos_t, torch::Tensor sin_t,
                       torch::Tensor block_table, torch::Tensor seq_ids,
-                      torch::Tensor positions, int64_t n_qheads, double eps) {
+                      torch::Tensor positions, int64_t n_qheads, double eps,
+                      c10::optional<torch::Tensor> k_scale,
+                      c10::optional<torch::Tensor> v_scale) {
+  const bool fp8 = kv_fp8_check("qk_rope_write_kv", kcache, vcache, k_scale,
+                                v_scale);
   const int T = positions.size(0);
   const int n_kvheads = kcache.size(1);
   const int head_dim = kcache.size(3);
@@ -314,13 +343,26 @@ void qk_rope_write_kv(torch::Tensor qkv, torch::Tensor kcache,
   const int max_blocks = block_table.size(1);
   dim3 grid(T, n_qheads + 2 * n_kvheads), block(head_dim);
   hipStream_t s = c10::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(qk_rope_write_kv_kernel, grid, block, 0, s,
-                     (short*)qkv.data_ptr(), (short*)kcache.data_ptr(),
-                     (short*)vcache.data_ptr(), (const short*)q_w.data_ptr(),
-                     (const short*)k_w.data_ptr(), cos_t.data_ptr<float>(),
-                     sin_t.data_ptr<float>(), block_table.data_ptr<int>(),
-                     seq_ids.data_ptr<int>(), positions.data_ptr<int>(),
-                     (int)n_qheads, n_kvheads, head_dim, max_blocks,
-                     row_stride, (float)eps);
+  if (fp8)
+    hipLaunchKernelGGL(qk_rope_write_kv_kernel<true>, grid, block, 0, s,
+                       (short*)qkv.data_ptr(), (uint8_t*)kcache.data_ptr(),
+                       (uint8_t*)vcache.data_ptr(),
+                       (const short*)q_w.data_ptr(),
+                       (const short*)k_w.data_ptr(), cos_t.data_ptr<float>(),
+                       sin_t.data_ptr<float>(), block_table.data_ptr<int>(),
+                       seq_ids.data_ptr<int>(), positions.data_ptr<int>(),
+                       (int)n_qheads, n_kvheads, head_dim, max_blocks,
+                       row_stride, (float)eps, k_scale->data_ptr<float>(),
+                       v_scale->data_ptr<float>());
+  else
+    hipLaunchKernelGGL(qk_rope_write_kv_kernel<false>, grid, block, 0, s,
+                       (short*)qkv.data_ptr(), (short*)kcache.data_ptr(),
+                       (short*)vcache.data_ptr(), (const short*)q_w.data_ptr(),
+                       (const short*)k_w.data_ptr(), cos_t.data_ptr<float>(),
+                       sin_t.data_ptr<float>(), block_table.data_ptr<int>(),
+                       seq_ids.data_ptr<int>(), positions.data_ptr<int>(),
+                       (int)n_qheads, n_kvheads, head_dim, max_blocks,
+                       row_stride, (float)eps, (float*)nullptr,
+                       (float*)nullptr);
   HIP_CHECK_KERNEL();
 }

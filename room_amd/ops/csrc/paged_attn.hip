@@ -19,6 +19,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
+#include "kv_fp8.h"
 
 #define BLOCK_SIZE 16
 #define CHUNK 32          // kv positions per iteration
@@ -31,16 +32,26 @@
 //   value phase: thread (h = t>>5, d4 = (t&31)*4) accumulates 4 output dims;
 //                V reads are 32×8B consecutive = coalesced per head-group.
 // Online softmax with per-head running max/sum (flash-style, fp32).
+//
+// F8 (all kernels of this file): the caches hold e4m3 bytes and kscale/vscale
+// [NB, Hk, BS] one f32 per row (kv_fp8.h). Bytes become the image's bf16
+// values as they are loaded; everything after the load is the bf16 code.
+template <bool F8>
+using kv_elem_t = std::conditional_t<F8, uint8_t, short>;
+
+template <bool F8>
 __global__ __launch_bounds__(256)
 void paged_attn_kernel(short* __restrict__ out,          // [T, Hq, D]
                        const short* __restrict__ q,      // [T, Hq, D]
-                       const short* __restrict__ kcache, // [NB, Hk, BS, D]
-                       const short* __restrict__ vcache,
+                       const kv_elem_t<F8>* __restrict__ kcache, // [NB, Hk, BS, D]
+                       const kv_elem_t<F8>* __restrict__ vcache,
                        const int* __restrict__ block_table,  // [S, MB]
                        const int* __restrict__ seq_ids,      // [T]
                        const int* __restrict__ q_pos,        // [T] absolute pos
                        int n_kvheads, int max_blocks, int q_row_stride,
-                       float scale) {
+                       float scale,
+                       const float* __restrict__ kscale,  // F8: [NB, Hk, BS]
+                       const float* __restrict__ vscale) {
   const int t = blockIdx.x;       // query token
   const int hk = blockIdx.y;      // kv head
   const int tid = threadIdx.x;
@@ -76,12 +87,20 @@ void paged_attn_kernel(short* __restrict__ out,          // [T, Hq, D]
       float s = -INFINITY;
       if (pos < bound) {
         const int blk = btab[pos / BLOCK_SIZE];
-        const short* krow = kcache + (long)blk * kv_stride_block
+        const kv_elem_t<F8>* krow = kcache + (long)blk * kv_stride_block
                             + ((long)hk * BLOCK_SIZE + (pos % BLOCK_SIZE)) * HEAD_DIM;
+        float ks = 1.f;
+        if constexpr (F8)
+          ks = kscale[((long)blk * n_kvheads + hk) * BLOCK_SIZE + pos % BLOCK_SIZE];
         float dot = 0.f;
         #pragma unroll
         for (int v8 = 0; v8 < HEAD_DIM / 8; ++v8) {
-          bf16x8 kv = *reinterpret_cast<const bf16x8*>(krow + v8 * 8);
+          bf16x8 kv;
+          if constexpr (F8)
+            kv = __builtin_bit_cast(bf16x8, kv_fp8x8_to_bf16(
+                *reinterpret_cast<const kv_u32x2*>(krow + v8 * 8), ks));
+          else
+            kv = *reinterpret_cast<const bf16x8*>(krow + v8 * 8);
           #pragma unroll
           for (int j = 0; j < 8; ++j) dot += q_s[h][v8 * 8 + j] * bf2f(kv[j]);
         }
@@ -107,10 +126,17 @@ void paged_attn_kernel(short* __restrict__ out,          // [T, Hq, D]
           l_run += w;
           const int pos = base + j;
           const int blk = btab[pos / BLOCK_SIZE];
-          const short* vrow = vcache + (long)blk * kv_stride_block
+          const kv_elem_t<F8>* vrow = vcache + (long)blk * kv_stride_block
                               + ((long)hk * BLOCK_SIZE + (pos % BLOCK_SIZE)) * HEAD_DIM
                               + sub * 4;
-          bf16x4 vv = *reinterpret_cast<const bf16x4*>(vrow);
+          bf16x4 vv;
+          if constexpr (F8)
+            vv = __builtin_bit_cast(bf16x4, kv_fp8x4_to_bf16(
+                *reinterpret_cast<const uint32_t*>(vrow),
+                vscale[((long)blk * n_kvheads + hk) * BLOCK_SIZE
+                       + pos % BLOCK_SIZE]));
+          else
+            vv = *reinterpret_cast<const bf16x4*>(vrow);
           acc[0] += w * bf2f(vv[0]);
           acc[1] += w * bf2f(vv[1]);
           acc[2] += w * bf2f(vv[2]);
@@ -166,7 +192,11 @@ __global__ void write_kv_kernel(short* __restrict__ kcache,
 
 void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
                      torch::Tensor vcache, torch::Tensor block_table,
-                     torch::Tensor seq_ids, torch::Tensor q_pos, double scale) {
+                     torch::Tensor seq_ids, torch::Tensor q_pos, double scale,
+                     c10::optional<torch::Tensor> k_scale,
+                     c10::optional<torch::Tensor> v_scale) {
+  const bool fp8 = kv_fp8_check("paged_attention", kcache, vcache, k_scale,
+                                v_scale);
   TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16);
   TORCH_CHECK(q.size(-1) == HEAD_DIM, "head_dim must be 128");
   const int T = q.size(0);
@@ -176,12 +206,24 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
   const int max_blocks = block_table.size(1);
   dim3 grid(T, n_kvheads), block(256);
   hipStream_t s = c10::hip::getCurrentHIPStream();
-  hipLaunchKernelGGL(paged_attn_kernel, grid, block, 0, s,
-                     (short*)out.data_ptr(), (const short*)q.data_ptr(),
-                     (const short*)kcache.data_ptr(), (const short*)vcache.data_ptr(),
-                     block_table.data_ptr<int>(), seq_ids.data_ptr<int>(),
-                     q_pos.data_ptr<int>(), n_kvheads, max_blocks,
-                     (int)q.stride(0), (float)scale);
+  if (fp8)
+    hipLaunchKernelGGL(paged_attn_kernel<true>, grid, block, 0, s,
+                       (short*)out.data_ptr(), (const short*)q.data_ptr(),
+                       (const uint8_t*)kcache.data_ptr(),
+                       (const uint8_t*)vcache.data_ptr(),
+                       block_table.data_ptr<int>(), seq_ids.data_ptr<int>(),
+                       q_pos.data_ptr<int>(), n_kvheads, max_blocks,
+                       (int)q.stride(0), (float)scale,
+                       k_scale->data_ptr<float>(), v_scale->data_ptr<float>());
+  else
+    hipLaunchKernelGGL(paged_attn_kernel<false>, grid, block, 0, s,
+                       (short*)out.data_ptr(), (const short*)q.data_ptr(),
+                       (const short*)kcache.data_ptr(),
+                       (const short*)vcache.data_ptr(),
+                       block_table.data_ptr<int>(), seq_ids.data_ptr<int>(),
+                       q_pos.data_ptr<int>(), n_kvheads, max_blocks,
+                       (int)q.stride(0), (float)scale,
+                       (const float*)nullptr, (const float*)nullptr);
   HIP_CHECK_KERNEL();
 }
 
@@ -250,23 +292,33 @@ void write_kv(torch::Tensor kcache, torch::Tensor vcache, torch::Tensor k,
 // Rows at positions >= hi load a valid row of the same block (clamped row
 // index, so p = 0 never meets uninitialised cache) and score -inf; a pair
 // without a second tile loads its first tile twice and masks the copy.
+//
+// F8: lane (n, g) loads 8 B where the bf16 form loads 16 B (the same 8
+// elements), plus the scales of the rows it reads: one for K row min(n, last)
+// and four for V rows min(4g + j, last), so every byte and every scale it
+// consumes belongs to a row < hi. All of a pair's loads still issue before
+// the first MFMA; the bytes are then converted into the same kr / vr
+// registers and the rest is shared.
 #define TILE 16
 #define SPLIT_WAVES 4
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
 // 3 waves per SIMD: 640 workgroups at B = 5 are 2.5 waves per SIMD. The bound
 // also keeps the accumulators in VGPRs, where the rescale can reach them.
+template <bool F8>
 __global__ __launch_bounds__(256, 3)
 void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
                              float* __restrict__ part_ml, // [T, Hq, NSPLITS, 2]
                              const short* __restrict__ q,
-                             const short* __restrict__ kcache,
-                             const short* __restrict__ vcache,
+                             const kv_elem_t<F8>* __restrict__ kcache,
+                             const kv_elem_t<F8>* __restrict__ vcache,
                              const int* __restrict__ block_table,
                              const int* __restrict__ seq_ids,
                              const int* __restrict__ q_pos,
                              int n_kvheads, int max_blocks, int q_row_stride,
-                             float scale) {
+                             float scale,
+                             const float* __restrict__ kscale,
+                             const float* __restrict__ vscale) {
   static_assert(TILE == BLOCK_SIZE, "a tile is one cache block");
   const int t = blockIdx.x;
   const int hk = blockIdx.y;
@@ -340,14 +392,54 @@ void paged_attn_split_kernel(float* __restrict__ part,   // [T, Hq, NSPLITS, D]
     }
   };
 
+  // F8: a lane's share of one tile as loaded, before conversion
+  struct RawTile { kv_u32x2 k[4], v[4]; float ks, vs[4]; };
+  auto issue_loads_f8 = [&](RawTile& r, int tile) {
+    const int blk = btab[tile];
+    const int last = min(hi - tile * TILE, TILE) - 1;   // last valid row
+    const long bh = (long)blk * n_kvheads + hk;         // wave-uniform
+    const char* kblk = reinterpret_cast<const char*>(kcache)
+                       + bh * (BLOCK_SIZE * HEAD_DIM);
+    const char* vblk = reinterpret_cast<const char*>(vcache)
+                       + bh * (BLOCK_SIZE * HEAD_DIM);
+    const int krow = min(n, last);
+    const unsigned koff = krow * HEAD_DIM + g * 8;
+    #pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+      r.k[ks] = *reinterpret_cast<const kv_u32x2*>(kblk + koff + ks * 32);
+    r.ks = kscale[bh * BLOCK_SIZE + krow];
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int vrow = min(4 * g + j, last);
+      r.v[j] = *reinterpret_cast<const kv_u32x2*>(vblk + vrow * HEAD_DIM + n * 8);
+      r.vs[j] = vscale[bh * BLOCK_SIZE + vrow];
+    }
+  };
+  auto convert_f8 = [&](bf16x8 (&kr)[4], u32x4 (&vr)[4], const RawTile& r) {
+    #pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+      kr[ks] = __builtin_bit_cast(bf16x8, kv_fp8x8_to_bf16(r.k[ks], r.ks));
+    #pragma unroll
+    for (int j = 0; j < 4; ++j) vr[j] = kv_fp8x8_to_bf16(r.v[j], r.vs[j]);
+  };
+
   for (int t0 = lo / TILE + wave; t0 < tile_end; t0 += 2 * SPLIT_WAVES) {
     const bool two = t0 + SPLIT_WAVES < tile_end;
     const int t1 = two ? t0 + SPLIT_WAVES : t0;
     bf16x8 k0[4], k1[4];
     u32x4 v0[4], v1[4];
-    issue_loads(k0, v0, t0);
-    issue_loads(k1, v1, t1);
-    __builtin_amdgcn_sched_barrier(0);   // keep the loads ahead of the MFMAs
+    if constexpr (F8) {
+      RawTile r0, r1;
+      issue_loads_f8(r0, t0);
+      issue_loads_f8(r1, t1);
+      __builtin_amdgcn_sched_barrier(0);
+      convert_f8(k0, v0, r0);
+      convert_f8(k1, v1, r1);
+    } else {
+      issue_loads(k0, v0, t0);
+      issue_loads(k1, v1, t1);
+      __builtin_amdgcn_sched_barrier(0);   // keep the loads ahead of the MFMAs
+    }
 
     f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0;
     #pragma unroll
@@ -476,7 +568,11 @@ void paged_attention_split(torch::Tensor out, torch::Tensor q,
                            torch::Tensor block_table, torch::Tensor seq_ids,
                            torch::Tensor q_pos, torch::Tensor part,
                            torch::Tensor part_ml, double scale,
-                           int64_t splits) {
+                           int64_t splits,
+                           c10::optional<torch::Tensor> k_scale,
+                           c10::optional<torch::Tensor> v_scale) {
+  const bool fp8 = kv_fp8_check("paged_attention_split", kcache, vcache,
+                                k_scale, v_scale);
   TORCH_CHECK(splits == 32 || splits == 64, "splits must be 32 or 64");
   // q may be a strided row-view into the packed qkv buffer
   TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == q.size(2));
@@ -492,12 +588,26 @@ void paged_attention_split(torch::Tensor out, torch::Tensor q,
   TORCH_CHECK(part.size(0) >= T && part.size(2) == NSPLITS_MAX);
   hipStream_t s = c10::hip::getCurrentHIPStream();
   dim3 g1(T, n_kvheads, (unsigned)splits);
-  hipLaunchKernelGGL(paged_attn_split_kernel, g1, dim3(256), 0, s,
-                     part.data_ptr<float>(), part_ml.data_ptr<float>(),
-                     (const short*)q.data_ptr(), (const short*)kcache.data_ptr(),
-                     (const short*)vcache.data_ptr(), block_table.data_ptr<int>(),
-                     seq_ids.data_ptr<int>(), q_pos.data_ptr<int>(),
-                     n_kvheads, max_blocks, (int)q.stride(0), (float)scale);
+  if (fp8)
+    hipLaunchKernelGGL(paged_attn_split_kernel<true>, g1, dim3(256), 0, s,
+                       part.data_ptr<float>(), part_ml.data_ptr<float>(),
+                       (const short*)q.data_ptr(),
+                       (const uint8_t*)kcache.data_ptr(),
+                       (const uint8_t*)vcache.data_ptr(),
+                       block_table.data_ptr<int>(), seq_ids.data_ptr<int>(),
+                       q_pos.data_ptr<int>(), n_kvheads, max_blocks,
+                       (int)q.stride(0), (float)scale,
+                       k_scale->data_ptr<float>(), v_scale->data_ptr<float>());
+  else
+    hipLaunchKernelGGL(paged_attn_split_kernel<false>, g1, dim3(256), 0, s,
+                       part.data_ptr<float>(), part_ml.data_ptr<float>(),
+                       (const short*)q.data_ptr(),
+                       (const short*)kcache.data_ptr(),
+                       (const short*)vcache.data_ptr(),
+                       block_table.data_ptr<int>(), seq_ids.data_ptr<int>(),
+                       q_pos.data_ptr<int>(), n_kvheads, max_blocks,
+                       (int)q.stride(0), (float)scale,
+                       (const float*)nullptr, (const float*)nullptr);
   HIP_CHECK_KERNEL();
   dim3 g2(T, n_qheads);
   if (splits == 64)

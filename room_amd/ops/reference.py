@@ -142,6 +142,40 @@ def dequantize_fp8_block(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return q.float() * s
 
 
+KV_FP8_MIN_EXP = -64   # smallest row-scale exponent of the fp8 KV cache
+
+
+def quantize_kv_rows(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Row-scaled e4m3 quantiser of the fp8 KV cache (kv_dtype="fp8"): the
+    row form of quantize_fp8_block. x: bf16 or f32 [..., D]; it is rounded to
+    bf16 first, as the cache writer sees bf16 rows. Returns (q, scale): q
+    float8_e4m3fn of x's shape, scale f32 [...] with one entry per row. A
+    row's scale is 2^e with e the smallest integer such that
+    amax ≤ 448·2^e, clamped to e ≥ −64 (1.0 for an all-zero row), and q is
+    the round-to-nearest-even e4m3 of x·2^−e. So |x/scale| ≤ 448, the cast
+    never saturates, and every q·scale is exactly a bf16 value. Plain torch;
+    runs on CPU and GPU."""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"quantize_kv_rows takes bf16 or f32, got {x.dtype}")
+    xb = x.to(torch.bfloat16).float()
+    amax = xb.abs().amax(dim=-1)
+    # frexp: amax = m · 2^E with m in [0.5, 1) and 448 = 0.875 · 2^9, so the
+    # exponent is E − 9, or E − 8 once m passes 0.875; no division, no log
+    m, e = torch.frexp(amax)
+    e = torch.where(m > 0.875, e - 8, e - 9).clamp_(min=KV_FP8_MIN_EXP)
+    one = torch.ones_like(amax)
+    scale = torch.where(amax > 0, torch.ldexp(one, e), one)
+    q = xb / scale.unsqueeze(-1)      # a power of two: the division is exact
+    return q.to(torch.float8_e4m3fn), scale
+
+
+def dequantize_kv_rows(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """f32 q.float() · scale with each row's scale over its D values. Every
+    value is exactly representable in bf16 (quantize_kv_rows), so
+    .to(bfloat16) of the result is the cache's bf16 image."""
+    return q.float() * scale.unsqueeze(-1)
+
+
 def vs_topk_ref(mat: torch.Tensor, query: torch.Tensor, k: int
                 ) -> tuple[torch.Tensor, torch.Tensor]:
     scores = mat.float() @ query.float()

@@ -6,6 +6,8 @@ environments (CI here) can import this module; calling any op raises.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from ..engine.step_plan import qtile_list
@@ -29,6 +31,21 @@ def _require():
         raise RuntimeError(
             f"room_amd._C not available (CPU-only environment?): {_import_error}")
     return _C
+
+
+@contextlib.contextmanager
+def check_only():
+    """Inside the block every op returns after its argument checks and before
+    its launch, and the tensors may live on any one device: for testing the
+    wrappers' contracts (csrc/checks.h). Process-wide; nothing in the engine
+    uses it."""
+    C = _require()
+    before = C.check_only()
+    C.set_check_only(True)
+    try:
+        yield
+    finally:
+        C.set_check_only(before)
 
 
 def rmsnorm(out: torch.Tensor, x: torch.Tensor, weight: torch.Tensor,

@@ -1,5 +1,6 @@
 // Python bindings for room_amd._C — the CDNA4 kernel library.
 #include <torch/extension.h>
+#include "checks.h"
 
 void rmsnorm(torch::Tensor out, torch::Tensor in, torch::Tensor weight, double eps);
 void fused_add_rmsnorm(torch::Tensor out, torch::Tensor residual, torch::Tensor in,
@@ -107,6 +108,10 @@ void encoder_pool(torch::Tensor out, torch::Tensor h, torch::Tensor cu_rows,
                   torch::Tensor mu, bool normalize);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("set_check_only", &set_check_only,
+        "process-wide: every op returns after its argument checks, before its "
+        "launch (for testing the checks); off by default");
+  m.def("check_only", &check_only, "whether check-only mode is on");
   m.def("rmsnorm", &rmsnorm, "RMSNorm (bf16, CDNA4)");
   m.def("fused_add_rmsnorm", &fused_add_rmsnorm, "residual += x; rmsnorm(residual)");
   m.def("qk_norm_rope", &qk_norm_rope, "fused per-head QK RMSNorm + RoPE");

@@ -19,6 +19,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
+#include "checks.h"
 
 #define ENC_DIM 384
 #define ENC_HEADS 12
@@ -254,35 +255,27 @@ void encoder_pool_kernel(float* __restrict__ out,            // [B, 384]
 
 // ---------------------------------------------------------------- wrappers
 
-namespace {
-
-void enc_check_cu(const torch::Tensor& cu_rows, const char* op) {
-  TORCH_CHECK(cu_rows.is_cuda() && cu_rows.dtype() == torch::kInt32
-              && cu_rows.dim() == 1 && cu_rows.is_contiguous()
-              && cu_rows.numel() >= 2,
-              op, ": cu_rows must be a contiguous int32 [B+1] device tensor");
+// R packed rows (1 <= R, R * 1152 within int) in B = cu_rows.numel() - 1
+// segments, 1 <= B <= R. The offsets themselves are the caller's contract
+// (ops._check_cu_rows checks them on host values).
+static int64_t enc_check_segments(OpChecks& c, const torch::Tensor& cu_rows,
+                                  int64_t R) {
+  c.range("R", R, 1, 0x7fffffffL / ENC_QKV);
+  c.tensor("cu_rows", cu_rows, kI32, {-1});
+  return c.size_range("cu_rows", cu_rows, 0, 2, R + 1) - 1;
 }
-
-}  // namespace
 
 void encoder_embed(torch::Tensor x, torch::Tensor feats, torch::Tensor pos_ids,
                    torch::Tensor pos_table) {
-  TORCH_CHECK(x.is_cuda() && x.dtype() == torch::kBFloat16 && x.dim() == 2
-              && x.size(1) == ENC_DIM && x.is_contiguous(),
-              "encoder_embed: x must be contiguous bf16 [R, 384]");
+  OpChecks c("encoder_embed");
+  c.tensor("x", x, kBF16, {-1, ENC_DIM});
   const int64_t R = x.size(0);
-  TORCH_CHECK(feats.is_cuda() && feats.dtype() == torch::kInt32
-              && feats.is_contiguous() && feats.dim() == 2
-              && feats.size(0) == R && feats.size(1) == 4,
-              "encoder_embed: feats must be contiguous int32 [R, 4]");
-  TORCH_CHECK(pos_ids.is_cuda() && pos_ids.dtype() == torch::kInt32
-              && pos_ids.is_contiguous() && pos_ids.numel() == R,
-              "encoder_embed: pos_ids must be contiguous int32 [R]");
-  TORCH_CHECK(pos_table.is_cuda() && pos_table.dtype() == torch::kFloat32
-              && pos_table.is_contiguous() && pos_table.dim() == 2
-              && pos_table.size(0) >= 1 && pos_table.size(1) == ENC_DIM,
-              "encoder_embed: pos_table must be contiguous f32 [P, 384]");
-  TORCH_CHECK(R >= 1 && R <= 0x7fffffffL / ENC_QKV);
+  c.range("R", R, 1, 0x7fffffffL / ENC_QKV);
+  c.tensor("feats", feats, kI32, {R, 4});
+  c.tensor("pos_ids", pos_ids, kI32, {R});
+  c.tensor("pos_table", pos_table, kF32, {-1, ENC_DIM});
+  c.size_range("pos_table", pos_table, 0, 1, std::numeric_limits<int>::max());
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(encoder_embed_kernel, dim3((R + 3) / 4), dim3(256), 0, s,
                      (short*)x.data_ptr(), feats.data_ptr<int>(),
@@ -293,19 +286,13 @@ void encoder_embed(torch::Tensor x, torch::Tensor feats, torch::Tensor pos_ids,
 
 void encoder_attention(torch::Tensor out, torch::Tensor qkv,
                        torch::Tensor cu_rows) {
-  TORCH_CHECK(qkv.is_cuda() && qkv.dtype() == torch::kBFloat16
-              && out.is_cuda() && out.dtype() == torch::kBFloat16,
-              "encoder_attention: qkv and out must be bf16 device tensors");
-  TORCH_CHECK(qkv.is_contiguous() && out.is_contiguous(),
-              "encoder_attention: qkv and out must be contiguous");
-  TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == ENC_QKV,
-              "encoder_attention: qkv rows are q|k|v, 1152 wide");
-  TORCH_CHECK(out.dim() == 2 && out.size(1) == ENC_DIM
-              && out.size(0) == qkv.size(0),
-              "encoder_attention: out must be [R, 384]");
-  enc_check_cu(cu_rows, "encoder_attention");
-  const int64_t R = qkv.size(0), B = cu_rows.numel() - 1;
-  TORCH_CHECK(R >= 1 && R <= 0x7fffffffL / ENC_QKV && B <= R);
+  OpChecks c("encoder_attention");
+  c.tensor("qkv", qkv, kBF16, {-1, ENC_QKV});   // rows are q|k|v
+  const int64_t R = qkv.size(0);
+  c.tensor("out", out, kBF16, {R, ENC_DIM});
+  const int64_t B = enc_check_segments(c, cu_rows, R);
+  c.grid(B, ENC_HEADS);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(encoder_attention_kernel, dim3(B, ENC_HEADS), dim3(256),
                      0, s, (short*)out.data_ptr(),
@@ -315,12 +302,14 @@ void encoder_attention(torch::Tensor out, torch::Tensor qkv,
 }
 
 void gelu_(torch::Tensor u) {
-  TORCH_CHECK(u.is_cuda() && u.dtype() == torch::kBFloat16 && u.is_contiguous(),
-              "gelu_: u must be a contiguous bf16 device tensor");
-  TORCH_CHECK(u.numel() % 8 == 0, "gelu_: element count must be a multiple of 8");
+  OpChecks c("gelu_");
+  c.require(u.defined(), "u is undefined");
+  c.tensor("u", u, kBF16, u.sizes());   // any shape, contiguous
+  c.require(u.numel() % 8 == 0, "u holds ", u.numel(),
+            " elements, not a multiple of 8");
   const long nvec = u.numel() / 8;
-  if (nvec == 0) return;
-  TORCH_CHECK((nvec + 255) / 256 <= 0x7fffffffL);
+  c.grid((nvec + 255) / 256);
+  if (nvec == 0 || check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(gelu_kernel, dim3((nvec + 255) / 256), dim3(256), 0, s,
                      (short*)u.data_ptr(), nvec);
@@ -329,19 +318,14 @@ void gelu_(torch::Tensor u) {
 
 void encoder_pool(torch::Tensor out, torch::Tensor h, torch::Tensor cu_rows,
                   torch::Tensor mu, bool normalize) {
-  TORCH_CHECK(h.is_cuda() && h.dtype() == torch::kBFloat16 && h.is_contiguous()
-              && h.dim() == 2 && h.size(1) == ENC_DIM,
-              "encoder_pool: h must be contiguous bf16 [R, 384]");
-  enc_check_cu(cu_rows, "encoder_pool");
-  const int64_t R = h.size(0), B = cu_rows.numel() - 1;
-  TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kFloat32
-              && out.is_contiguous() && out.dim() == 2 && out.size(0) == B
-              && out.size(1) == ENC_DIM,
-              "encoder_pool: out must be contiguous f32 [B, 384]");
-  TORCH_CHECK(mu.is_cuda() && mu.dtype() == torch::kFloat32
-              && mu.is_contiguous() && mu.numel() == ENC_DIM,
-              "encoder_pool: mu must be contiguous f32 [384]");
-  TORCH_CHECK(R >= 1 && R <= 0x7fffffffL / ENC_QKV && B <= R);
+  OpChecks c("encoder_pool");
+  c.tensor("h", h, kBF16, {-1, ENC_DIM});
+  const int64_t R = h.size(0);
+  const int64_t B = enc_check_segments(c, cu_rows, R);
+  c.tensor("out", out, kF32, {B, ENC_DIM});
+  c.tensor("mu", mu, kF32, {ENC_DIM});
+  c.grid(B);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(encoder_pool_kernel, dim3(B), dim3(192), 0, s,
                      out.data_ptr<float>(), (const short*)h.data_ptr(),

@@ -20,6 +20,7 @@
 #include <c10/hip/HIPStream.h>
 #include "common.h"
 #include "kv_fp8.h"
+#include "checks.h"
 
 #define FP_BS 16          // paged KV block size
 #define FP_QTOK 32        // q tokens per tile (2 MFMA row-blocks)
@@ -268,31 +269,14 @@ void flash_prefill(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
                    torch::Tensor tile_desc, double scale,
                    c10::optional<torch::Tensor> k_scale,
                    c10::optional<torch::Tensor> v_scale) {
-  const bool fp8 = kv_fp8_check("flash_prefill", kcache, vcache, k_scale,
-                                v_scale);
-  TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16);
-  TORCH_CHECK(q.dim() == 3 && q.size(-1) == FP_D, "q is [T, Hq, 128]");
-  TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == FP_D);  // strided row-views OK
-  // everything the kernel indexes is checked here: a wrong shape must be a
-  // Python error, never an out-of-bounds access
-  TORCH_CHECK(out.is_cuda() && out.dtype() == torch::kBFloat16 &&
-              out.is_contiguous() && out.sizes() == q.sizes(),
-              "out must be contiguous bf16 shaped like q");
-  TORCH_CHECK(tile_desc.is_cuda() && tile_desc.dtype() == torch::kInt32 &&
-              tile_desc.dim() == 2 && tile_desc.size(1) == 2 &&
-              tile_desc.is_contiguous(), "tile_desc is contiguous int32 [G, 2]");
-  TORCH_CHECK(seq_ids.is_cuda() && q_pos.is_cuda() &&
-              seq_ids.dtype() == torch::kInt32 &&
-              q_pos.dtype() == torch::kInt32 &&
-              seq_ids.is_contiguous() && q_pos.is_contiguous() &&
-              seq_ids.numel() == q.size(0) && q_pos.numel() == q.size(0),
-              "seq_ids and q_pos are int32 with one entry per q row");
-  TORCH_CHECK(block_table.is_cuda() && block_table.dtype() == torch::kInt32 &&
-              block_table.dim() == 2 && block_table.is_contiguous(),
-              "block_table is contiguous int32 [seqs, max_blocks]");
+  OpChecks c("flash_prefill");
+  const bool fp8 = kv_fp8_check(c, kcache, vcache, k_scale, v_scale);
+  attn_check_tokens(c, out, q, kcache, block_table, seq_ids, q_pos);
+  c.tensor("tile_desc", tile_desc, kI32, {-1, 2});
   const int n_kvheads = kcache.size(1);
-  TORCH_CHECK(q.size(1) == n_kvheads * FP_QH);
-  const int G = tile_desc.size(0);
+  const int G = c.fits_int("tile_desc.size(0)", tile_desc.size(0));
+  c.grid(G, n_kvheads);
+  if (check_only()) return;
   const int max_blocks = block_table.size(1);
   dim3 grid(G, n_kvheads), block(512);
   hipStream_t s = c10::hip::getCurrentHIPStream();

@@ -7,6 +7,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
+#include "checks.h"
 
 #define GEMV_MAXB 8
 // gemv_addnorm's waves per workgroup: 8 measured fastest of 4, 8 and 16 at
@@ -183,16 +184,31 @@ static void gemv_launch(void* y, const short* x, const short* w, int B, int H,
     GEMV_CASE(1) GEMV_CASE(2) GEMV_CASE(3) GEMV_CASE(4)
     GEMV_CASE(5) GEMV_CASE(6) GEMV_CASE(7) GEMV_CASE(8)
 #undef GEMV_CASE
-    default: TORCH_CHECK(false, "gemv handles B<=8");
+    default: TORCH_CHECK(false, "gemv: B = ", B, " must be in 1..8");
   }
 }
 
+// What the three GEMV ops share: x [B, H] bf16 with 1 <= B <= 8 (decode) and H
+// a multiple of 512, w [N, H] bf16, and y [B, N] of the given dtype.
+struct GemvDims { int B, H, N; };
+static GemvDims gemv_check(OpChecks& c, const char* yname,
+                           const torch::Tensor& y, torch::ScalarType ydtype,
+                           const torch::Tensor& x, const torch::Tensor& w,
+                           int rows_per_block) {
+  c.tensor("x", x, kBF16, {-1, -1});
+  const int B = c.size_range("x", x, 0, 1, GEMV_MAXB);
+  const int H = c.size_multiple("x", x, 1, WAVE * 8);
+  c.tensor("w", w, kBF16, {-1, H});
+  const int N = c.fits_int("w.size(0)", w.size(0));
+  c.tensor(yname, y, ydtype, {B, N});
+  c.grid((N + rows_per_block - 1) / rows_per_block);
+  return {B, H, N};
+}
+
 void gemv(torch::Tensor y, torch::Tensor x, torch::Tensor w) {
-  const int B = x.size(0), H = x.size(1), N = w.size(0);
-  TORCH_CHECK(B >= 1 && B <= GEMV_MAXB,
-              "gemv handles B<=8 (decode); use hipBLASLt above");
-  TORCH_CHECK(x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16);
-  TORCH_CHECK(H % (WAVE * 8) == 0, "H must be a multiple of 512");
+  OpChecks c("gemv");
+  const auto [B, H, N] = gemv_check(c, "y", y, bf16_or_f32(y), x, w, 4);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   #define GEMV_GO(FO, NIT) gemv_launch<FO, NIT>( \
       y.data_ptr(), (const short*)x.data_ptr(), (const short*)w.data_ptr(), \
@@ -237,13 +253,9 @@ void gemv_residual_kernel(short* __restrict__ r,           // [BN, N] in/out
 }
 
 void gemv_residual(torch::Tensor r, torch::Tensor x, torch::Tensor w) {
-  const int B = x.size(0), H = x.size(1), N = w.size(0);
-  TORCH_CHECK(B >= 1 && B <= GEMV_MAXB, "gemv_residual handles B<=8 (decode)");
-  TORCH_CHECK(x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16 &&
-              r.dtype() == torch::kBFloat16);
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && r.is_contiguous());
-  TORCH_CHECK(w.size(1) == H && r.size(0) == B && r.size(1) == N);
-  TORCH_CHECK(H % (WAVE * 8) == 0, "H must be a multiple of 512");
+  OpChecks c("gemv_residual");
+  const auto [B, H, N] = gemv_check(c, "r", r, kBF16, x, w, 4);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   dim3 grid((N + 3) / 4), block(256);
   #define GEMV_RES2(BN, NIT) hipLaunchKernelGGL( \
@@ -441,7 +453,8 @@ static void gemv_addnorm_launch(size_t lds, hipStream_t s, void* y,
   auto k = gemv_addnorm_kernel<DELTA, BN, NIT, WPB>;
   if (lds + 4 * BN * sizeof(float) > 64 * 1024)
     TORCH_CHECK(hipFuncSetAttribute((const void*)k,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess);
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
+        "gemv_addnorm: could not raise the dynamic LDS limit to ", lds);
   hipLaunchKernelGGL(k, dim3((N + WPB - 1) / WPB), dim3(WPB * WAVE), lds, s,
                      y, x, d, x_out, g, w, H, N, eps, f32out);
 }
@@ -449,20 +462,24 @@ static void gemv_addnorm_launch(size_t lds, hipStream_t s, void* y,
 void gemv_addnorm(torch::Tensor y, torch::Tensor x, torch::Tensor delta,
                   torch::Tensor x_out, torch::Tensor gamma, torch::Tensor w,
                   double eps) {
-  const int B = x.size(0), H = x.size(1), N = w.size(0);
-  TORCH_CHECK(B >= 1 && B <= GEMV_MAXB && H % (WAVE * 8) == 0 && N >= 1);
-  TORCH_CHECK(x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16);
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && y.is_contiguous() &&
-              gamma.is_contiguous() && delta.is_contiguous());
-  const bool has_delta = delta.numel() > 0;
-  TORCH_CHECK(!has_delta || (delta.numel() == x.numel() &&
-                             x_out.numel() == x.numel() &&
-                             x_out.data_ptr() != x.data_ptr()));
+  OpChecks c("gemv_addnorm");
+  const auto [B, H, N] =
+      gemv_check(c, "y", y, bf16_or_f32(y), x, w, GEMV_ADDNORM_WPB);
+  c.require(N >= 1, "w holds no row");
+  c.tensor("gamma", gamma, kBF16, {H});
+  c.tensor("x_out", x_out, kBF16, {B, H});
+  // delta with no element: a plain norm + gemv, x_out is not written
+  const bool has_delta = delta.defined() && delta.numel() > 0;
+  if (has_delta) {
+    c.tensor("delta", delta, bf16_or_f32(delta), {B, H});
+    c.require(x_out.data_ptr() != x.data_ptr(), "x_out must not alias x");
+  }
   const int dmode = !has_delta ? 0 : delta.dtype() == torch::kFloat32 ? 2 : 1;
-  TORCH_CHECK(dmode != 1 || delta.dtype() == torch::kBFloat16);
   const int f32out = y.dtype() == torch::kFloat32;
   const size_t lds = (size_t)B * H * sizeof(short);  // staged normed rows
-  TORCH_CHECK(lds <= 128 * 1024, "B*H too large for LDS staging");
+  c.require(lds <= 128 * 1024, "B*H = ", (int64_t)B * H,
+            " too large for LDS staging");
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   const void* dptr = has_delta ? delta.data_ptr() : nullptr;
   #define AN_GO(D, BN, NIT) gemv_addnorm_launch<D, BN, NIT>( \

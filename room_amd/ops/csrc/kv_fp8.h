@@ -13,40 +13,7 @@
 
 #define KV_FP8_MIN_EXP (-64)
 
-// Wrapper-side check shared by the four ops (the including file has
-// torch/extension.h): scales are given exactly when the caches are e4m3.
-// Returns whether this is the fp8 form.
-inline bool kv_fp8_check(const char* op, const torch::Tensor& kcache,
-                         const torch::Tensor& vcache,
-                         const c10::optional<torch::Tensor>& k_scale,
-                         const c10::optional<torch::Tensor>& v_scale) {
-  TORCH_CHECK(kcache.is_cuda() && vcache.is_cuda() &&
-              kcache.is_contiguous() && vcache.is_contiguous() &&
-              kcache.dim() == 4 && kcache.size(2) == 16 &&
-              kcache.size(3) == 128 && vcache.sizes() == kcache.sizes() &&
-              kcache.dtype() == vcache.dtype(),
-              op, ": caches are contiguous [NB, Hk, 16, 128], equally shaped "
-              "and of one dtype");
-  const bool fp8 = kcache.dtype() == torch::kFloat8_e4m3fn;
-  TORCH_CHECK(fp8 || kcache.dtype() == torch::kBFloat16, op,
-              ": caches must be bfloat16 or float8_e4m3fn");
-  const bool scales = k_scale.has_value() && v_scale.has_value();
-  TORCH_CHECK(scales || (!k_scale.has_value() && !v_scale.has_value()), op,
-              ": k_scale and v_scale go together");
-  TORCH_CHECK(!fp8 || scales, op,
-              ": float8_e4m3fn caches need k_scale and v_scale");
-  TORCH_CHECK(fp8 || !scales, op,
-              ": k_scale / v_scale given with bfloat16 caches");
-  if (fp8) {
-    for (const torch::Tensor* s : {&*k_scale, &*v_scale})
-      TORCH_CHECK(s->is_cuda() && s->dtype() == torch::kFloat32 &&
-                  s->is_contiguous() && s->dim() == 3 &&
-                  s->size(0) == kcache.size(0) &&
-                  s->size(1) == kcache.size(1) && s->size(2) == 16, op,
-                  ": scales must be contiguous float32 [NB, Hk, 16]");
-  }
-  return fp8;
-}
+// (The wrapper-side check of the four ops is kv_fp8_check in checks.h.)
 
 // Row scale from the row's largest |bf16| bit pattern (0..0x7f7f), in integer
 // arithmetic. amax = 1.m * 2^(be - 127) and 448 = 1.75 * 2^8, so

@@ -14,6 +14,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
+#include "checks.h"
 
 // ---------------------------------------------------------------- router
 // softmax over E<=128 logits, pick top-K<=8, renormalize their probs.
@@ -428,12 +429,39 @@ void moe_gemv_down_kernel(float* __restrict__ out,         // [T, H] f32
 
 // ---------------------------------------------------------------- wrappers
 
+// What the three routers share: E <= 128 experts, 1 <= K <= min(8, E) picks,
+// and topk_ids [rows, K] int32, topk_w [rows, K] f32 to hold them.
+static void router_check(OpChecks& c, const torch::Tensor& topk_ids,
+                         const torch::Tensor& topk_w, int64_t rows, int64_t E,
+                         int64_t K) {
+  c.range("E", E, 1, 128);
+  c.range("K", K, 1, std::min<int64_t>(8, E));
+  c.tensor("topk_ids", topk_ids, kI32, {rows, K});
+  c.tensor("topk_w", topk_w, kF32, {rows, K});
+}
+
+// The decode routers' GEMV: x [B, H] bf16 rows (at most 8) against wr [E, H]
+// bf16, every quarter of H in 8-wide vectors.
+struct RouterDims { int B, H, E; };
+static RouterDims router_gemv_check(OpChecks& c, const char* xname,
+                                    const torch::Tensor& x,
+                                    const torch::Tensor& wr, int min_rows) {
+  c.tensor(xname, x, kBF16, {-1, -1});
+  const int B = c.size_range(xname, x, 0, min_rows, 8);
+  const int H = c.size_multiple(xname, x, 1, RS * 8);
+  c.tensor("wr", wr, kBF16, {-1, H});
+  return {B, H, c.fits_int("wr.size(0)", wr.size(0))};
+}
+
 void moe_router(torch::Tensor topk_ids, torch::Tensor topk_w, torch::Tensor logits,
                 int64_t K) {
-  const int T = logits.size(0), E = logits.size(1);
-  TORCH_CHECK(E <= 128 && K >= 1 && K <= 8 && K <= E,
-              "router kernel handles E<=128, 1<=K<=min(8,E)");
-  TORCH_CHECK(logits.dtype() == torch::kFloat32);
+  OpChecks c("moe_router");
+  c.tensor("logits", logits, kF32, {-1, -1});
+  const int T = c.fits_int("logits.size(0)", logits.size(0));
+  const int E = c.fits_int("logits.size(1)", logits.size(1));
+  router_check(c, topk_ids, topk_w, T, E, K);
+  c.grid(T);
+  if (check_only()) return;
   dim3 grid(T), block(WAVE);
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(moe_router_kernel, grid, block, 0, s,
@@ -457,12 +485,10 @@ static float* router_partials(int B, int E, c10::Device dev) {
 
 void router_gemv_topk(torch::Tensor topk_ids, torch::Tensor topk_w,
                       torch::Tensor x, torch::Tensor wr, int64_t K) {
-  const int B = x.size(0), H = x.size(1), E = wr.size(0);
-  TORCH_CHECK(E <= 128 && K <= 8 && B <= 8);
-  TORCH_CHECK(H % (RS * WAVE * 8) == 0 || (H / RS) % 8 == 0,
-              "H/RS must be a multiple of 8");
-  TORCH_CHECK(x.dtype() == torch::kBFloat16 && wr.dtype() == torch::kBFloat16);
-  TORCH_CHECK(x.is_contiguous() && wr.is_contiguous());
+  OpChecks c("router_gemv_topk");
+  const auto [B, H, E] = router_gemv_check(c, "x", x, wr, 0);
+  router_check(c, topk_ids, topk_w, B, E, K);
+  if (check_only()) return;
   float* yp = router_partials(B, E, x.device());
   hipStream_t s = c10::hip::getCurrentHIPStream();
   dim3 g1((E + 3) / 4, RS);
@@ -480,17 +506,12 @@ void router_norm_gemv_topk(torch::Tensor topk_ids, torch::Tensor topk_w,
                            torch::Tensor hbuf, torch::Tensor r,
                            torch::Tensor gamma, torch::Tensor wr, int64_t K,
                            double eps) {
-  const int B = r.size(0), H = r.size(1), E = wr.size(0);
-  TORCH_CHECK(E <= 128 && K >= 1 && K <= 8 && K <= E && B >= 1 && B <= 8);
-  TORCH_CHECK(H % (RS * 8) == 0, "H/RS must be a multiple of 8");
-  TORCH_CHECK(r.dtype() == torch::kBFloat16 && wr.dtype() == torch::kBFloat16 &&
-              gamma.dtype() == torch::kBFloat16 &&
-              hbuf.dtype() == torch::kBFloat16);
-  TORCH_CHECK(r.is_contiguous() && wr.is_contiguous() && hbuf.is_contiguous() &&
-              gamma.is_contiguous());
-  TORCH_CHECK(wr.size(1) == H && gamma.numel() == H && hbuf.size(0) == B &&
-              hbuf.size(1) == H);
-  TORCH_CHECK(topk_ids.numel() == (long)B * K && topk_w.numel() == (long)B * K);
+  OpChecks c("router_norm_gemv_topk");
+  const auto [B, H, E] = router_gemv_check(c, "r", r, wr, 1);
+  router_check(c, topk_ids, topk_w, B, E, K);
+  c.tensor("hbuf", hbuf, kBF16, {B, H});
+  c.tensor("gamma", gamma, kBF16, {H});
+  if (check_only()) return;
   float* yp = router_partials(B, E, r.device());
   hipStream_t s = c10::hip::getCurrentHIPStream();
   dim3 g1((E + 3) / 4, B);
@@ -511,20 +532,17 @@ void router_norm_gemv_topk(torch::Tensor topk_ids, torch::Tensor topk_w,
 void moe_gemv_h(torch::Tensor h, torch::Tensor x, torch::Tensor w13,
                 torch::Tensor pair_token, torch::Tensor pair_expert,
                 torch::Tensor out_zero) {
-  const int P = pair_token.size(0);
-  const int H = x.size(-1), I = h.size(-1);
+  OpChecks c("moe_gemv_h");
+  moe_gemv_h_check(c, h, x, pair_token, pair_expert, out_zero);
+  const int P = h.size(0), I = h.size(1);
+  const int H = c.size_multiple("x", x, 1, WAVE * 8);
+  bf16_check_weights(c, "w13", w13, 2 * (int64_t)I, H);
+  if (check_only()) return;
   dim3 grid(P, (I + 3) / 4), block(256);
-  float* zp = nullptr;
-  long zn = 0;
-  if (out_zero.defined() && out_zero.numel() > 0) {
-    TORCH_CHECK(out_zero.dtype() == torch::kFloat32);
-    zp = out_zero.data_ptr<float>();
-    zn = out_zero.numel();
-    TORCH_CHECK(zn <= (long)grid.x * grid.y * block.x,
-                "zero target larger than grid coverage");
-  }
+  const bool zero = out_zero.defined() && out_zero.numel() > 0;
+  float* zp = zero ? out_zero.data_ptr<float>() : nullptr;
+  const long zn = zero ? out_zero.numel() : 0;
   hipStream_t s = c10::hip::getCurrentHIPStream();
-  TORCH_CHECK(H % (WAVE * 8) == 0, "H must be a multiple of 512");
   #define MOE_H_GO(NIT) hipLaunchKernelGGL( \
       moe_gemv_h_kernel<NIT>, grid, block, 0, s, (short*)h.data_ptr(), \
       (const short*)x.data_ptr(), (const short*)w13.data_ptr(), \
@@ -537,10 +555,11 @@ void moe_gemv_h(torch::Tensor h, torch::Tensor x, torch::Tensor w13,
 void moe_gemv_down(torch::Tensor out, torch::Tensor h, torch::Tensor w2,
                    torch::Tensor pair_w, torch::Tensor pair_token,
                    torch::Tensor pair_expert) {
-  const int P = pair_token.size(0);
-  const int H = out.size(-1), I = h.size(-1);
-  TORCH_CHECK(out.dtype() == torch::kFloat32);
-  TORCH_CHECK(I % (16 * 8) == 0, "I must be a multiple of 128");
+  OpChecks c("moe_gemv_down");
+  moe_gemv_down_check(c, out, h, pair_w, pair_token, pair_expert);
+  const int P = h.size(0), H = out.size(1), I = h.size(1);
+  bf16_check_weights(c, "w2", w2, H, I);
+  if (check_only()) return;
   dim3 grid(P, (H + 15) / 16), block(256);   // 16 outputs per WG
   hipStream_t s = c10::hip::getCurrentHIPStream();
   #define MOE_DOWN_GO(NIT) hipLaunchKernelGGL( \
@@ -706,26 +725,11 @@ void moe_grouped_gemm128_kernel(short* __restrict__ out,      // [P, N]
 
 void moe_grouped_gemm128(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                          torch::Tensor pair_token, torch::Tensor tile_desc) {
-  const int H = x.size(-1), N = out.size(-1);
-  const int G = tile_desc.size(0);
-  TORCH_CHECK(H % G2_BK == 0 && N % G2_BN == 0);
-  // a wrong shape must be a Python error, never an out-of-bounds access
-  TORCH_CHECK(x.is_cuda() && w.is_cuda() && out.is_cuda() &&
-              x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16 &&
-              out.dtype() == torch::kBFloat16, "x, w and out must be bf16");
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous(),
-              "x, w and out must be contiguous");
-  TORCH_CHECK(x.dim() == 2 && out.dim() == 2, "x is [T, H], out is [P, N]");
-  TORCH_CHECK(w.dim() == 3 && w.size(1) == N && w.size(2) == H,
-              "w is [E, N, H]");
-  TORCH_CHECK(pair_token.is_cuda() && pair_token.dtype() == torch::kInt32 &&
-              pair_token.is_contiguous() &&
-              pair_token.numel() == out.size(0),
-              "pair_token is int32 with one entry per out row");
-  TORCH_CHECK(tile_desc.is_cuda() && tile_desc.dtype() == torch::kInt32 &&
-              tile_desc.dim() == 2 && tile_desc.is_contiguous(),
-              "tile_desc is contiguous int32 [G, 3]");
-  TORCH_CHECK(tile_desc.size(1) == 3, "desc is [G,3]; n-tile comes from grid.y");
+  OpChecks c("moe_grouped_gemm128");
+  grouped_gemm_check(c, false, out, x, pair_token, tile_desc);
+  const int H = x.size(1), N = out.size(1), G = tile_desc.size(0);
+  bf16_check_weights(c, "w", w, N, H);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   dim3 grid(G, N / G2_BN), block(512);
   hipLaunchKernelGGL((moe_grouped_gemm128_kernel<G2_BM, G2_BN>), grid, block, 0, s,
@@ -779,23 +783,16 @@ __global__ void moe_combine_gather_kernel(short* __restrict__ out,  // [T, H] bf
 
 void moe_combine_gather(torch::Tensor out, torch::Tensor z, torch::Tensor topk_w,
                         torch::Tensor inv_order) {
-  const int T = out.size(0), H = out.size(-1);
-  const int K = topk_w.size(-1);
-  TORCH_CHECK(K <= 8 && out.dtype() == torch::kBFloat16);
-  // a wrong shape must be a Python error, never an out-of-bounds access
-  TORCH_CHECK(out.is_cuda() && out.dim() == 2 && out.is_contiguous(),
-              "out is contiguous [T, H]");
-  TORCH_CHECK(z.is_cuda() && z.dtype() == torch::kBFloat16 &&
-              z.is_contiguous() && z.dim() == 2 && z.size(1) == H,
-              "z is contiguous bf16 [P, H]");
-  TORCH_CHECK(H % 8 == 0, "H must be a multiple of 8");
-  TORCH_CHECK(topk_w.is_cuda() && topk_w.dtype() == torch::kFloat32 &&
-              topk_w.dim() == 2 && topk_w.size(0) == T && K >= 1 &&
-              topk_w.is_contiguous(), "topk_w is contiguous f32 [T, K]");
-  TORCH_CHECK(inv_order.is_cuda() && inv_order.dtype() == torch::kInt32 &&
-              inv_order.is_contiguous() &&
-              inv_order.numel() == (int64_t)T * K,
-              "inv_order is int32 with T*K entries");
+  OpChecks c("moe_combine_gather");
+  c.tensor("out", out, kBF16, {-1, -1});
+  const int T = c.fits_int("out.size(0)", out.size(0));
+  const int H = c.size_multiple("out", out, 1, 8);
+  c.tensor("z", z, kBF16, {-1, H});
+  c.tensor("topk_w", topk_w, kF32, {T, -1});
+  const int K = c.size_range("topk_w", topk_w, 1, 1, 8);
+  c.tensor("inv_order", inv_order, kI32, {(int64_t)T * K});
+  c.grid(T);
+  if (check_only()) return;
   dim3 grid(T), block(256);
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(moe_combine_gather_kernel, grid, block, 0, s,
@@ -829,10 +826,13 @@ __global__ void moe_build_desc_kernel(int* __restrict__ desc,      // [GMAX, 3]
 }
 
 void moe_build_desc(torch::Tensor desc, torch::Tensor counts, int64_t bm) {
-  const int E = counts.numel();
-  const int gmax = desc.size(0);
-  TORCH_CHECK(counts.dtype() == torch::kInt64 && desc.size(1) == 3);
-  TORCH_CHECK(bm >= 1 && bm <= G2_BM, "tile height 1..128");
+  OpChecks c("moe_build_desc");
+  c.tensor("desc", desc, kI32, {-1, 3});
+  c.tensor("counts", counts, kI64, {-1});
+  const int E = c.fits_int("counts.size(0)", counts.size(0));
+  const int gmax = c.fits_int("desc.size(0)", desc.size(0));
+  c.range("bm", bm, 1, G2_BM);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(moe_build_desc_kernel, dim3(1), dim3(64), 0, s,
                      desc.data_ptr<int>(), counts.data_ptr<long>(), E, (int)bm,

@@ -15,6 +15,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
+#include "checks.h"
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
@@ -368,62 +369,21 @@ void skinny_gemm_fp8_kernel(void* __restrict__ out,             // [rows, N]
 
 // ---------------------------------------------------------------- wrappers
 
-namespace {
-
-// weights [E, N, K] e4m3fn with scales [E, N/128, K/128] f32
-void fp8_check_weights(const torch::Tensor& q, const torch::Tensor& s,
-                       const char* what) {
-  TORCH_CHECK(q.dtype() == torch::kFloat8_e4m3fn, what,
-              ": weights must be float8_e4m3fn");
-  TORCH_CHECK(s.dtype() == torch::kFloat32, what, ": scales must be f32");
-  TORCH_CHECK(q.dim() == 3 && s.dim() == 3, what,
-              ": weights are [E, N, K], scales [E, N/128, K/128]");
-  TORCH_CHECK(q.is_contiguous() && s.is_contiguous(), what,
-              ": weights and scales must be contiguous");
-  TORCH_CHECK(q.size(0) >= 1 && q.size(1) >= FP8_BLK && q.size(2) >= FP8_BLK
-              && q.size(1) % FP8_BLK == 0 && q.size(2) % FP8_BLK == 0, what,
-              ": N and K must be multiples of 128");
-  TORCH_CHECK(s.size(0) == q.size(0) && s.size(1) == q.size(1) / FP8_BLK
-              && s.size(2) == q.size(2) / FP8_BLK, what,
-              ": scale shape must be [E, N/128, K/128]");
-  TORCH_CHECK(q.is_cuda() && s.is_cuda(), what, ": tensors must be on the GPU");
-}
-
-void fp8_check_pairs(const torch::Tensor& pair_token,
-                     const torch::Tensor& pair_expert, int64_t P) {
-  TORCH_CHECK(pair_token.dtype() == torch::kInt32
-              && pair_expert.dtype() == torch::kInt32
-              && pair_token.is_contiguous() && pair_expert.is_contiguous()
-              && pair_token.numel() == P && pair_expert.numel() == P,
-              "pair_token and pair_expert: contiguous int32 [P]");
-}
-
-}  // namespace
-
 void moe_gemv_h_fp8(torch::Tensor h, torch::Tensor x, torch::Tensor w13_q,
                     torch::Tensor w13_s, torch::Tensor pair_token,
                     torch::Tensor pair_expert, torch::Tensor out_zero) {
-  fp8_check_weights(w13_q, w13_s, "moe_gemv_h_fp8");
-  TORCH_CHECK(x.dim() == 2 && h.dim() == 2);
+  OpChecks c("moe_gemv_h_fp8");
+  moe_gemv_h_check(c, h, x, pair_token, pair_expert, out_zero);
   const int64_t P = h.size(0), H = x.size(1), I = h.size(1);
-  TORCH_CHECK(x.dtype() == torch::kBFloat16 && h.dtype() == torch::kBFloat16,
-              "moe_gemv_h_fp8: x and h must be bf16");
-  TORCH_CHECK(x.is_contiguous() && h.is_contiguous(),
-              "moe_gemv_h_fp8: x and h must be contiguous");
-  TORCH_CHECK(w13_q.size(2) == H && w13_q.size(1) == 2 * I && I % FP8_BLK == 0,
-              "moe_gemv_h_fp8: w13 is [E, 2I, H] with I a multiple of 128");
-  TORCH_CHECK(P >= 1 && P <= 0x7fffffffL && I / 4 <= 65535);
-  fp8_check_pairs(pair_token, pair_expert, P);
+  c.require(P >= 1, "h holds no row");
+  c.size_multiple("h", h, 1, FP8_BLK);
+  c.size_multiple("x", x, 1, FP8_BLK);
+  fp8_check_weights(c, "w13_q", w13_q, "w13_s", w13_s, 2 * I, H);
+  if (check_only()) return;
   dim3 grid(P, (I + 3) / 4), block(256);
-  float* zp = nullptr;
-  long zn = 0;
-  if (out_zero.defined() && out_zero.numel() > 0) {
-    TORCH_CHECK(out_zero.dtype() == torch::kFloat32 && out_zero.is_contiguous());
-    zp = out_zero.data_ptr<float>();
-    zn = out_zero.numel();
-    TORCH_CHECK(zn <= (long)grid.x * grid.y * block.x,
-                "zero target larger than grid coverage");
-  }
+  const bool zero = out_zero.defined() && out_zero.numel() > 0;
+  float* zp = zero ? out_zero.data_ptr<float>() : nullptr;
+  const long zn = zero ? out_zero.numel() : 0;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   #define MOE_H8_GO(NIT) hipLaunchKernelGGL( \
       moe_gemv_h_fp8_kernel<NIT>, grid, block, 0, s, (short*)h.data_ptr(), \
@@ -438,19 +398,13 @@ void moe_gemv_h_fp8(torch::Tensor h, torch::Tensor x, torch::Tensor w13_q,
 void moe_gemv_down_fp8(torch::Tensor out, torch::Tensor h, torch::Tensor w2_q,
                        torch::Tensor w2_s, torch::Tensor pair_w,
                        torch::Tensor pair_token, torch::Tensor pair_expert) {
-  fp8_check_weights(w2_q, w2_s, "moe_gemv_down_fp8");
-  TORCH_CHECK(out.dim() == 2 && h.dim() == 2);
+  OpChecks c("moe_gemv_down_fp8");
+  moe_gemv_down_check(c, out, h, pair_w, pair_token, pair_expert);
   const int64_t P = h.size(0), H = out.size(1), I = h.size(1);
-  TORCH_CHECK(out.dtype() == torch::kFloat32 && h.dtype() == torch::kBFloat16,
-              "moe_gemv_down_fp8: out must be f32, h bf16");
-  TORCH_CHECK(out.is_contiguous() && h.is_contiguous(),
-              "moe_gemv_down_fp8: out and h must be contiguous");
-  TORCH_CHECK(w2_q.size(1) == H && w2_q.size(2) == I,
-              "moe_gemv_down_fp8: w2 is [E, H, I]");
-  TORCH_CHECK(P >= 1 && P <= 0x7fffffffL && H / 16 <= 65535);
-  fp8_check_pairs(pair_token, pair_expert, P);
-  TORCH_CHECK(pair_w.dtype() == torch::kFloat32 && pair_w.is_contiguous()
-              && pair_w.numel() == P, "pair_w: contiguous f32 [P]");
+  c.require(P >= 1, "h holds no row");
+  c.size_multiple("out", out, 1, FP8_BLK);
+  fp8_check_weights(c, "w2_q", w2_q, "w2_s", w2_s, H, I);
+  if (check_only()) return;
   dim3 grid(P, (H + 15) / 16), block(256);   // 16 outputs per WG
   hipStream_t s = c10::hip::getCurrentHIPStream();
   #define MOE_DOWN8_GO(NIT) hipLaunchKernelGGL( \
@@ -495,25 +449,11 @@ void moe_grouped_gemm_skinny_fp8(torch::Tensor out, torch::Tensor x,
                                  torch::Tensor w_q, torch::Tensor w_s,
                                  torch::Tensor pair_token,
                                  torch::Tensor tile_desc) {
-  fp8_check_weights(w_q, w_s, "moe_grouped_gemm_skinny_fp8");
-  TORCH_CHECK(x.dim() == 2 && out.dim() == 2);
-  const int64_t K = x.size(1), N = w_q.size(1);
-  TORCH_CHECK(w_q.size(2) == K && out.size(1) == N,
-              "moe_grouped_gemm_skinny_fp8: shape mismatch");
-  TORCH_CHECK(x.dtype() == torch::kBFloat16,
-              "moe_grouped_gemm_skinny_fp8: x must be bf16");
-  TORCH_CHECK(out.dtype() == torch::kBFloat16 || out.dtype() == torch::kFloat32,
-              "moe_grouped_gemm_skinny_fp8: out must be bf16 or f32");
-  TORCH_CHECK(x.is_contiguous() && out.is_contiguous(),
-              "moe_grouped_gemm_skinny_fp8: x and out must be contiguous");
-  TORCH_CHECK(pair_token.dtype() == torch::kInt32 && pair_token.is_contiguous()
-              && pair_token.numel() == out.size(0),
-              "pair_token: int32 [rows of out]");
-  TORCH_CHECK(tile_desc.dtype() == torch::kInt32 && tile_desc.is_contiguous()
-              && tile_desc.dim() == 2 && tile_desc.size(1) == 3,
-              "desc is int32 [G,3] with m_size <= 16");
-  const int64_t G = tile_desc.size(0);
-  TORCH_CHECK(G >= 1 && G <= 65535);
+  OpChecks c("moe_grouped_gemm_skinny_fp8");
+  grouped_gemm_check(c, true, out, x, pair_token, tile_desc);
+  const int64_t K = x.size(1), N = out.size(1), G = tile_desc.size(0);
+  fp8_check_weights(c, "w_q", w_q, "w_s", w_s, N, K);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   const int f32out = out.dtype() == torch::kFloat32;
   skf_dispatch_u(out.data_ptr(), (const short*)x.data_ptr(),
@@ -539,28 +479,12 @@ void moe_grouped_gemm128_fp8(torch::Tensor out, torch::Tensor x,
                              torch::Tensor w_q, torch::Tensor w_s,
                              torch::Tensor pair_token,
                              torch::Tensor tile_desc) {
-  fp8_check_weights(w_q, w_s, "moe_grouped_gemm128_fp8");
-  TORCH_CHECK(x.dim() == 2 && out.dim() == 2,
-              "moe_grouped_gemm128_fp8: x is [T, K], out is [P, N]");
-  const int64_t K = x.size(1), N = w_q.size(1);
-  TORCH_CHECK(w_q.size(2) == K && out.size(1) == N,
-              "moe_grouped_gemm128_fp8: shape mismatch");
-  TORCH_CHECK(x.is_cuda() && out.is_cuda() && x.dtype() == torch::kBFloat16
-              && out.dtype() == torch::kBFloat16,
-              "moe_grouped_gemm128_fp8: x and out must be bf16 on the GPU");
-  TORCH_CHECK(x.is_contiguous() && out.is_contiguous(),
-              "moe_grouped_gemm128_fp8: x and out must be contiguous");
-  TORCH_CHECK(pair_token.is_cuda() && pair_token.dtype() == torch::kInt32
-              && pair_token.is_contiguous()
-              && pair_token.numel() == out.size(0),
-              "pair_token is int32 with one entry per out row");
-  TORCH_CHECK(tile_desc.is_cuda() && tile_desc.dtype() == torch::kInt32
-              && tile_desc.dim() == 2 && tile_desc.is_contiguous()
-              && tile_desc.size(1) == 3,
-              "tile_desc is contiguous int32 [G, 3]");
-  const int64_t G = tile_desc.size(0);
-  TORCH_CHECK(G >= 1 && G <= 0x7fffffffL && N / 64 <= 65535
-              && K <= 0x7fffffffL);
+  OpChecks c("moe_grouped_gemm128_fp8");
+  grouped_gemm_check(c, false, out, x, pair_token, tile_desc);
+  const int64_t K = x.size(1), N = out.size(1), G = tile_desc.size(0);
+  c.require(G >= 1, "tile_desc holds no tile");
+  fp8_check_weights(c, "w_q", w_q, "w_s", w_s, N, K);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   moe_grouped_gemm128_fp8_launch(
       (short*)out.data_ptr(), (const short*)x.data_ptr(),

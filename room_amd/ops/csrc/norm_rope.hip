@@ -9,6 +9,7 @@
 #include <c10/hip/HIPStream.h>
 #include "common.h"
 #include "kv_fp8.h"
+#include "checks.h"
 
 // ---------------------------------------------------------------- rmsnorm
 // y = x / rms(x) * w.   rows × cols, cols % 8 == 0, cols <= 8192.
@@ -169,11 +170,14 @@ __global__ void silu_mul_kernel(short* __restrict__ out,        // [rows, inter]
 // ---------------------------------------------------------------- host wrappers
 
 void rmsnorm(torch::Tensor out, torch::Tensor in, torch::Tensor weight, double eps) {
-  TORCH_CHECK(in.is_cuda() && in.dtype() == torch::kBFloat16);
-  TORCH_CHECK(in.is_contiguous() && out.is_contiguous());
-  long rows = in.numel() / in.size(-1);
-  int cols = in.size(-1);
-  TORCH_CHECK(cols % 8 == 0);
+  OpChecks c("rmsnorm");
+  c.tensor("in", in, kBF16, {-1, -1});
+  const int64_t rows = in.size(0);
+  const int cols = c.size_multiple("in", in, 1, 8);
+  c.tensor("out", out, kBF16, {rows, cols});
+  c.tensor("weight", weight, kBF16, {cols});
+  c.grid(rows);
+  if (check_only()) return;
   dim3 grid(rows), block(256);
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(rmsnorm_kernel, grid, block, 0, s,
@@ -184,10 +188,15 @@ void rmsnorm(torch::Tensor out, torch::Tensor in, torch::Tensor weight, double e
 
 void fused_add_rmsnorm(torch::Tensor out, torch::Tensor residual, torch::Tensor in,
                        torch::Tensor weight, double eps) {
-  TORCH_CHECK(in.is_cuda());
-  long rows = in.numel() / in.size(-1);
-  int cols = in.size(-1);
-  TORCH_CHECK(cols % 8 == 0);
+  OpChecks c("fused_add_rmsnorm");
+  c.tensor("in", in, bf16_or_f32(in), {-1, -1});   // bf16, or the MoE f32 sum
+  const int64_t rows = in.size(0);
+  const int cols = c.size_multiple("in", in, 1, 8);
+  c.tensor("residual", residual, kBF16, {rows, cols});
+  c.tensor("out", out, kBF16, {rows, cols});
+  c.tensor("weight", weight, kBF16, {cols});
+  c.grid(rows);
+  if (check_only()) return;
   dim3 grid(rows), block(256);
   hipStream_t s = c10::hip::getCurrentHIPStream();
   if (in.dtype() == torch::kFloat32) {
@@ -196,7 +205,6 @@ void fused_add_rmsnorm(torch::Tensor out, torch::Tensor residual, torch::Tensor 
                        in.data_ptr(), (const short*)weight.data_ptr(),
                        cols, (float)eps);
   } else {
-    TORCH_CHECK(in.dtype() == torch::kBFloat16);
     hipLaunchKernelGGL(fused_add_rmsnorm_kernel<false>, grid, block, 0, s,
                        (short*)out.data_ptr(), (short*)residual.data_ptr(),
                        in.data_ptr(), (const short*)weight.data_ptr(),
@@ -205,13 +213,26 @@ void fused_add_rmsnorm(torch::Tensor out, torch::Tensor residual, torch::Tensor 
   HIP_CHECK_KERNEL();
 }
 
+// cos_t / sin_t [max_pos, 64] f32: positions index their rows (caller's
+// contract, like every index tensor's contents)
 void qk_norm_rope(torch::Tensor q, torch::Tensor k, torch::Tensor q_w,
                   torch::Tensor k_w, torch::Tensor cos_t, torch::Tensor sin_t,
                   torch::Tensor positions, int64_t n_qheads, int64_t n_kvheads,
                   int64_t head_dim, double eps) {
-  TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16);
-  TORCH_CHECK(head_dim == 128, "kernel assumes head_dim=128");
-  int T = positions.size(0);
+  OpChecks c("qk_norm_rope");
+  c.require(head_dim == 128, "head_dim = ", head_dim, " but the kernel assumes 128");
+  c.tensor("positions", positions, kI32, {-1});
+  const int64_t T = positions.size(0);
+  c.tensor("q", q, kBF16, {T, n_qheads, head_dim});
+  c.tensor("k", k, kBF16, {T, n_kvheads, head_dim});
+  c.tensor("q_w", q_w, kBF16, {head_dim});
+  c.tensor("k_w", k_w, kBF16, {head_dim});
+  c.tensor("cos_t", cos_t, kF32, {-1, head_dim / 2});
+  c.tensor("sin_t", sin_t, kF32, {cos_t.size(0), head_dim / 2});
+  c.range("n_qheads", n_qheads, 0, 65535);
+  c.range("n_kvheads", n_kvheads, 0, 65535);
+  c.grid(T, n_qheads + n_kvheads);
+  if (check_only()) return;
   dim3 grid(T, n_qheads + n_kvheads), block(head_dim);
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(qk_norm_rope_kernel, grid, block, 0, s,
@@ -224,10 +245,14 @@ void qk_norm_rope(torch::Tensor q, torch::Tensor k, torch::Tensor q_w,
 }
 
 void silu_mul(torch::Tensor out, torch::Tensor gateup) {
-  TORCH_CHECK(gateup.is_cuda() && gateup.dtype() == torch::kBFloat16);
-  long rows = gateup.numel() / gateup.size(-1);
-  int inter = gateup.size(-1) / 2;
-  TORCH_CHECK(inter % 8 == 0);
+  OpChecks c("silu_mul");
+  c.tensor("gateup", gateup, kBF16, {-1, -1});
+  const int64_t rows = gateup.size(0);
+  // rows are gate | up, each half in 8-wide vectors
+  const int inter = c.size_multiple("gateup", gateup, 1, 16) / 2;
+  c.tensor("out", out, kBF16, {rows, inter});
+  c.grid(rows);
+  if (check_only()) return;
   dim3 grid(rows), block(256);
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(silu_mul_kernel, grid, block, 0, s,
@@ -331,15 +356,23 @@ void qk_rope_write_kv(torch::Tensor qkv, torch::Tensor kcache,
                       torch::Tensor positions, int64_t n_qheads, double eps,
                       c10::optional<torch::Tensor> k_scale,
                       c10::optional<torch::Tensor> v_scale) {
-  const bool fp8 = kv_fp8_check("qk_rope_write_kv", kcache, vcache, k_scale,
-                                v_scale);
-  const int T = positions.size(0);
+  OpChecks c("qk_rope_write_kv");
+  const bool fp8 = kv_fp8_check(c, kcache, vcache, k_scale, v_scale);
   const int n_kvheads = kcache.size(1);
-  const int head_dim = kcache.size(3);
-  TORCH_CHECK(head_dim == 128 && kcache.size(2) == 16);
-  TORCH_CHECK(qkv.dim() == 2 && qkv.is_contiguous());
-  const int row_stride = qkv.size(1);
-  TORCH_CHECK(row_stride == (n_qheads + 2 * n_kvheads) * head_dim);
+  const int head_dim = 128;
+  c.range("n_qheads", n_qheads, 0, 65535);
+  c.tensor("positions", positions, kI32, {-1});   // one per qkv row
+  const int64_t T = positions.size(0);
+  check_paging(c, block_table, seq_ids, T);
+  const int row_stride =
+      c.fits_int("qkv row", (n_qheads + 2 * n_kvheads) * head_dim);
+  c.tensor("qkv", qkv, kBF16, {T, row_stride});
+  c.tensor("q_w", q_w, kBF16, {head_dim});
+  c.tensor("k_w", k_w, kBF16, {head_dim});
+  c.tensor("cos_t", cos_t, kF32, {-1, head_dim / 2});
+  c.tensor("sin_t", sin_t, kF32, {cos_t.size(0), head_dim / 2});
+  c.grid(T, n_qheads + 2 * n_kvheads);
+  if (check_only()) return;
   const int max_blocks = block_table.size(1);
   dim3 grid(T, n_qheads + 2 * n_kvheads), block(head_dim);
   hipStream_t s = c10::hip::getCurrentHIPStream();

@@ -20,6 +20,7 @@
 #include <c10/hip/HIPStream.h>
 #include "common.h"
 #include "kv_fp8.h"
+#include "checks.h"
 
 #define BLOCK_SIZE 16
 #define CHUNK 32          // kv positions per iteration
@@ -195,14 +196,12 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
                      torch::Tensor seq_ids, torch::Tensor q_pos, double scale,
                      c10::optional<torch::Tensor> k_scale,
                      c10::optional<torch::Tensor> v_scale) {
-  const bool fp8 = kv_fp8_check("paged_attention", kcache, vcache, k_scale,
-                                v_scale);
-  TORCH_CHECK(q.is_cuda() && q.dtype() == torch::kBFloat16);
-  TORCH_CHECK(q.size(-1) == HEAD_DIM, "head_dim must be 128");
-  const int T = q.size(0);
+  OpChecks c("paged_attention");
+  const bool fp8 = kv_fp8_check(c, kcache, vcache, k_scale, v_scale);
+  const int T = attn_check_tokens(c, out, q, kcache, block_table, seq_ids, q_pos);
   const int n_kvheads = kcache.size(1);
-  TORCH_CHECK(q.size(1) == n_kvheads * QH_PER_KV, "GQA group must be 8");
-  TORCH_CHECK(kcache.size(2) == BLOCK_SIZE);
+  c.grid(T, n_kvheads);
+  if (check_only()) return;
   const int max_blocks = block_table.size(1);
   dim3 grid(T, n_kvheads), block(256);
   hipStream_t s = c10::hip::getCurrentHIPStream();
@@ -230,8 +229,18 @@ void paged_attention(torch::Tensor out, torch::Tensor q, torch::Tensor kcache,
 void write_kv(torch::Tensor kcache, torch::Tensor vcache, torch::Tensor k,
               torch::Tensor v, torch::Tensor block_table, torch::Tensor seq_ids,
               torch::Tensor q_pos) {
-  const int T = k.size(0);
-  const int n_kvheads = kcache.size(1);
+  OpChecks c("write_kv");
+  // bf16 caches only: the fp8 writer is qk_rope_write_kv
+  c.tensor("kcache", kcache, kBF16, {-1, -1, BLOCK_SIZE, HEAD_DIM});
+  c.tensor("vcache", vcache, kBF16, kcache.sizes());
+  const int n_kvheads = c.fits_int("kcache.size(1)", kcache.size(1));
+  c.tensor("k", k, kBF16, {-1, n_kvheads, HEAD_DIM});
+  const int T = c.fits_int("k.size(0)", k.size(0));
+  c.tensor("v", v, kBF16, {T, n_kvheads, HEAD_DIM});
+  check_paging(c, block_table, seq_ids, T);
+  c.tensor("q_pos", q_pos, kI32, {T});
+  c.grid(T);
+  if (check_only()) return;
   const int max_blocks = block_table.size(1);
   dim3 grid(T), block(128);
   hipStream_t s = c10::hip::getCurrentHIPStream();
@@ -571,21 +580,22 @@ void paged_attention_split(torch::Tensor out, torch::Tensor q,
                            int64_t splits,
                            c10::optional<torch::Tensor> k_scale,
                            c10::optional<torch::Tensor> v_scale) {
-  const bool fp8 = kv_fp8_check("paged_attention_split", kcache, vcache,
-                                k_scale, v_scale);
-  TORCH_CHECK(splits == 32 || splits == 64, "splits must be 32 or 64");
-  // q may be a strided row-view into the packed qkv buffer
-  TORCH_CHECK(q.stride(2) == 1 && q.stride(1) == q.size(2));
-  // the split kernel loads q, K and V in 16-byte vectors
-  TORCH_CHECK(q.size(2) == HEAD_DIM && q.stride(0) % 8 == 0 &&
-              reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
-              "q rows must be 16-byte aligned, head_dim 128");
-  TORCH_CHECK(kcache.size(2) == BLOCK_SIZE);
-  const int T = q.size(0);
+  OpChecks c("paged_attention_split");
+  const bool fp8 = kv_fp8_check(c, kcache, vcache, k_scale, v_scale);
+  c.require(splits == 32 || splits == 64, "splits = ", splits,
+            " must be 32 or 64");
+  const int T = attn_check_tokens(c, out, q, kcache, block_table, seq_ids, q_pos);
   const int n_kvheads = kcache.size(1);
   const int n_qheads = n_kvheads * QH_PER_KV;
+  // the partials may be allocated for more tokens than this call has
+  c.tensor("part", part, kF32, {-1, n_qheads, NSPLITS_MAX, HEAD_DIM});
+  c.tensor("part_ml", part_ml, kF32, {-1, n_qheads, NSPLITS_MAX, 2});
+  c.require(part.size(0) >= T && part_ml.size(0) >= T,
+            "part and part_ml hold fewer than the ", T, " tokens of q");
+  c.grid(T, n_kvheads, splits);
+  c.grid(T, n_qheads);
+  if (check_only()) return;
   const int max_blocks = block_table.size(1);
-  TORCH_CHECK(part.size(0) >= T && part.size(2) == NSPLITS_MAX);
   hipStream_t s = c10::hip::getCurrentHIPStream();
   dim3 g1(T, n_kvheads, (unsigned)splits);
   if (fp8)

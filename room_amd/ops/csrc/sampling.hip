@@ -33,6 +33,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
+#include "checks.h"
 
 #define SMP_THREADS 256
 #define SMP_MAXK 64
@@ -276,32 +277,24 @@ void sample_rows(torch::Tensor out_tokens, torch::Tensor logits,
                  torch::Tensor presence_penalty,
                  torch::Tensor frequency_penalty, torch::Tensor repeat_last_n,
                  torch::Tensor ring, torch::Tensor ring_len, bool append) {
-  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous());
-  const int B = logits.size(0), V = logits.size(1);
-  TORCH_CHECK(logits.dtype() == torch::kFloat32);
-  TORCH_CHECK(V >= 1 && V <= V4_NSC * SMP_MAXSPAN,
-              "sample_rows: vocabulary above ", V4_NSC * SMP_MAXSPAN);
-  auto row_vec = [&](const torch::Tensor& t, torch::ScalarType ty,
-                     const char* name) {
-    TORCH_CHECK(t.dtype() == ty && t.numel() == B && t.is_contiguous() &&
-                t.device() == logits.device(), "sample_rows: bad ", name);
-  };
-  row_vec(out_tokens, torch::kInt32, "out_tokens");
-  row_vec(temperature, torch::kFloat32, "temperature");
-  row_vec(top_p, torch::kFloat32, "top_p");
-  row_vec(top_k, torch::kInt32, "top_k");
-  row_vec(seeds, torch::kInt64, "seeds");
-  row_vec(ctr, torch::kInt32, "ctr");
-  row_vec(repetition_penalty, torch::kFloat32, "repetition_penalty");
-  row_vec(presence_penalty, torch::kFloat32, "presence_penalty");
-  row_vec(frequency_penalty, torch::kFloat32, "frequency_penalty");
-  row_vec(repeat_last_n, torch::kInt32, "repeat_last_n");
-  row_vec(ring_len, torch::kInt32, "ring_len");
-  TORCH_CHECK(ring.dtype() == torch::kInt32 && ring.dim() == 2 &&
-              ring.size(0) == B && ring.size(1) == SMP_RING &&
-              ring.is_contiguous() && ring.device() == logits.device(),
-              "sample_rows: ring must be [B, ", SMP_RING, "] int32");
-  if (B == 0) return;
+  OpChecks c("sample_rows");
+  c.tensor("logits", logits, kF32, {-1, -1});
+  const int B = c.fits_int("logits.size(0)", logits.size(0));
+  const int V = c.size_range("logits", logits, 1, 1, V4_NSC * SMP_MAXSPAN);
+  c.tensor("out_tokens", out_tokens, kI32, {B});
+  c.tensor("temperature", temperature, kF32, {B});
+  c.tensor("top_p", top_p, kF32, {B});
+  c.tensor("top_k", top_k, kI32, {B});
+  c.tensor("seeds", seeds, kI64, {B});
+  c.tensor("ctr", ctr, kI32, {B});
+  c.tensor("repetition_penalty", repetition_penalty, kF32, {B});
+  c.tensor("presence_penalty", presence_penalty, kF32, {B});
+  c.tensor("frequency_penalty", frequency_penalty, kF32, {B});
+  c.tensor("repeat_last_n", repeat_last_n, kI32, {B});
+  c.tensor("ring_len", ring_len, kI32, {B});
+  c.tensor("ring", ring, kI32, {B, SMP_RING});
+  c.grid(B, V4_NSC);
+  if (B == 0 || check_only()) return;
   // persistent per-B scratch: keeps the op allocation-free inside hipGraph
   // capture (the engine's decode graphs replay this kernel pair)
   static std::unordered_map<int, std::pair<torch::Tensor, torch::Tensor>> scratch;
@@ -349,7 +342,14 @@ __global__ void hist_append_kernel(int* __restrict__ hist,   // [KMAX * B]
 
 void hist_append(torch::Tensor hist, torch::Tensor ctr, torch::Tensor toks,
                  int64_t kmax) {
-  const int B = toks.numel();
+  OpChecks c("hist_append");
+  c.tensor("toks", toks, kI32, {-1});
+  // one thread per token, one block
+  const int B = c.size_range("toks", toks, 0, 0, 1024);
+  c.range("kmax", kmax, 0, std::numeric_limits<int>::max() / std::max(B, 1));
+  c.tensor("hist", hist, kI32, {kmax * B});
+  c.tensor("ctr", ctr, kI32, {1});
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(hist_append_kernel, dim3(1), dim3(std::max(B, 64)), 0, s,
                      hist.data_ptr<int>(), ctr.data_ptr<int>(),

@@ -43,6 +43,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
+#include "checks.h"
 
 // MF: 16-row MFMA fragments per tile (BM = 16·MF). NW: waves per workgroup
 // (the K split). U: chunks per wave with loads in flight together, (1+MF)·8
@@ -226,29 +227,19 @@ void sk_dispatch(int MF, int NW, void* out, const short* x, const short* w,
   }
 }
 
-void sk_check_common(const torch::Tensor& out, const torch::Tensor& x,
-                     const torch::Tensor& w, int64_t K, int64_t N) {
-  TORCH_CHECK(x.dtype() == torch::kBFloat16 && w.dtype() == torch::kBFloat16,
-              "skinny gemm: x and w must be bf16");
-  TORCH_CHECK(out.dtype() == torch::kBFloat16 || out.dtype() == torch::kFloat32,
-              "skinny gemm: out must be bf16 or f32");
-  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous(),
-              "skinny gemm: x, w and out must be contiguous");
-  TORCH_CHECK(K >= 64 && K % 64 == 0, "skinny gemm: K must be a multiple of 64");
-  TORCH_CHECK(N >= 16 && N % 16 == 0, "skinny gemm: N must be a multiple of 16");
-  TORCH_CHECK(N / 16 <= 0x7fffffffL);
-}
-
 }  // namespace
 
 // y[M,N] = x[M,K] @ w[N,K]^T, 1 ≤ M ≤ 64: one tile, height from M
 void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w) {
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && y.dim() == 2);
-  const int64_t M = x.size(0), K = x.size(1), N = w.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64, "skinny_gemm handles 1 <= M <= 64 rows");
-  TORCH_CHECK(w.size(1) == K && y.size(0) == M && y.size(1) == N,
-              "skinny_gemm: shape mismatch");
-  sk_check_common(y, x, w, K, N);
+  OpChecks c("skinny_gemm");
+  c.tensor("x", x, kBF16, {-1, -1});
+  const int64_t M = c.size_range("x", x, 0, 1, 64);   // one tile, height from M
+  const int64_t K = c.size_multiple("x", x, 1, 64);
+  c.tensor("w", w, kBF16, {-1, K});
+  const int64_t N = c.size_multiple("w", w, 0, 16);
+  c.tensor("y", y, bf16_or_f32(y), {M, N});
+  c.grid(N / 16);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   sk_dispatch((int)(M + 15) / 16, sk_waves(false, (int)K, (int)N),
               y.data_ptr(), (const short*)x.data_ptr(),
@@ -261,19 +252,11 @@ void skinny_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w) {
 void moe_grouped_gemm_skinny(torch::Tensor out, torch::Tensor x,
                              torch::Tensor w, torch::Tensor pair_token,
                              torch::Tensor tile_desc) {
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 3 && out.dim() == 2);
-  const int64_t K = x.size(1), N = w.size(1);
-  TORCH_CHECK(w.size(2) == K && out.size(1) == N,
-              "moe_grouped_gemm_skinny: shape mismatch");
-  sk_check_common(out, x, w, K, N);
-  TORCH_CHECK(pair_token.dtype() == torch::kInt32 && pair_token.is_contiguous()
-              && pair_token.numel() == out.size(0),
-              "pair_token: int32 [rows of out]");
-  TORCH_CHECK(tile_desc.dtype() == torch::kInt32 && tile_desc.is_contiguous()
-              && tile_desc.dim() == 2 && tile_desc.size(1) == 3,
-              "desc is int32 [G,3] with m_size <= 16");
-  const int64_t G = tile_desc.size(0);
-  TORCH_CHECK(G >= 1 && G <= 65535);
+  OpChecks c("moe_grouped_gemm_skinny");
+  grouped_gemm_check(c, true, out, x, pair_token, tile_desc);
+  const int64_t K = x.size(1), N = out.size(1), G = tile_desc.size(0);
+  bf16_check_weights(c, "w", w, N, K);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   sk_dispatch(1, sk_waves(true, (int)K, (int)N), out.data_ptr(),
               (const short*)x.data_ptr(), (const short*)w.data_ptr(),

@@ -15,6 +15,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 #include "common.h"
+#include "checks.h"
 
 #define VS_DIM 384
 #define VS_MAXK 64
@@ -111,11 +112,19 @@ __global__ void vs_merge_kernel(float* __restrict__ out_v,  // [K]
 void vs_topk(torch::Tensor out_v, torch::Tensor out_i, torch::Tensor cand_v,
              torch::Tensor cand_i, torch::Tensor mat, torch::Tensor query,
              int64_t K) {
-  TORCH_CHECK(mat.dtype() == torch::kBFloat16 && mat.size(1) == VS_DIM);
-  TORCH_CHECK(query.dtype() == torch::kFloat32 && query.numel() == VS_DIM);
-  TORCH_CHECK(K >= 1 && K <= VS_MAXK);
-  const long N = mat.size(0);
-  const int nblocks = (int)cand_v.size(0);
+  OpChecks c("vs_topk");
+  c.range("K", K, 1, VS_MAXK);
+  c.tensor("mat", mat, kBF16, {-1, VS_DIM});
+  const int N = c.fits_int("mat.size(0)", mat.size(0));
+  c.tensor("query", query, kF32, {VS_DIM});
+  c.tensor("cand_v", cand_v, kF32, {-1, K});
+  const int nblocks = c.fits_int("cand_v.size(0)", cand_v.size(0));
+  c.fits_int("cand_v.numel()", nblocks * K);
+  c.tensor("cand_i", cand_i, kI32, {nblocks, K});
+  c.tensor("out_v", out_v, kF32, {K});
+  c.tensor("out_i", out_i, kI64, {K});
+  c.grid(nblocks);
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   hipLaunchKernelGGL(vs_score_topk_kernel, dim3(nblocks), dim3(VS_BLOCK), 0, s,
                      cand_v.data_ptr<float>(), cand_i.data_ptr<int>(),
@@ -395,33 +404,21 @@ void vs_topk_scoped(torch::Tensor out_v, torch::Tensor out_i,
                     torch::Tensor cand_v, torch::Tensor cand_i,
                     torch::Tensor mat, torch::Tensor tags,
                     torch::Tensor queries, torch::Tensor scopes, int64_t K) {
-  TORCH_CHECK(mat.is_cuda() && tags.is_cuda() && queries.is_cuda() &&
-              scopes.is_cuda() && out_v.is_cuda() && out_i.is_cuda() &&
-              cand_v.is_cuda() && cand_i.is_cuda(),
-              "vs_topk_scoped: all tensors must live on the GPU");
-  TORCH_CHECK(mat.dtype() == torch::kBFloat16 && mat.dim() == 2 &&
-              mat.size(1) == VS_DIM && mat.is_contiguous());
-  TORCH_CHECK(mat.size(0) < (1LL << 31), "vs_topk_scoped: N must be < 2^31");
-  const long N = mat.size(0);
-  TORCH_CHECK(tags.dtype() == torch::kInt32 && tags.is_contiguous() &&
-              tags.numel() == N, "vs_topk_scoped: tags must be int32 [N]");
-  TORCH_CHECK(queries.dtype() == torch::kFloat32 && queries.dim() == 2 &&
-              queries.size(1) == VS_DIM && queries.is_contiguous());
-  const long Q = queries.size(0);
-  TORCH_CHECK(Q >= 1 && Q <= VS_MAXQ, "vs_topk_scoped: 1 <= Q <= 8");
-  TORCH_CHECK(scopes.dtype() == torch::kInt32 && scopes.is_contiguous() &&
-              scopes.numel() == Q, "vs_topk_scoped: scopes must be int32 [Q]");
-  TORCH_CHECK(K >= 1 && K <= VS_MAXK);
-  TORCH_CHECK(cand_v.dtype() == torch::kFloat32 && cand_v.is_contiguous() &&
-              cand_i.dtype() == torch::kInt32 && cand_i.is_contiguous() &&
-              cand_v.dim() == 3 && cand_v.size(0) == Q && cand_v.size(2) == K &&
-              cand_v.size(1) >= 1 && cand_v.size(1) <= WAVE * VS_MLISTS &&
-              cand_i.sizes() == cand_v.sizes(),
-              "vs_topk_scoped: candidates must be [Q, nblocks <= 512, K]");
-  TORCH_CHECK(out_v.dtype() == torch::kFloat32 && out_v.is_contiguous() &&
-              out_i.dtype() == torch::kInt64 && out_i.is_contiguous() &&
-              out_v.numel() == Q * K && out_i.numel() == Q * K);
-  const int nblocks = (int)cand_v.size(1);
+  OpChecks c("vs_topk_scoped");
+  c.range("K", K, 1, VS_MAXK);
+  c.tensor("mat", mat, kBF16, {-1, VS_DIM});
+  const long N = c.fits_int("mat.size(0)", mat.size(0));
+  c.tensor("tags", tags, kI32, {N});
+  c.tensor("queries", queries, kF32, {-1, VS_DIM});
+  const long Q = c.size_range("queries", queries, 0, 1, VS_MAXQ);
+  c.tensor("scopes", scopes, kI32, {Q});
+  // the merge wave holds every block's list head: at most 512 blocks
+  c.tensor("cand_v", cand_v, kF32, {Q, -1, K});
+  const int nblocks = c.size_range("cand_v", cand_v, 1, 1, WAVE * VS_MLISTS);
+  c.tensor("cand_i", cand_i, kI32, {Q, nblocks, K});
+  c.tensor("out_v", out_v, kF32, {Q, K});
+  c.tensor("out_i", out_i, kI64, {Q, K});
+  if (check_only()) return;
   hipStream_t s = c10::hip::getCurrentHIPStream();
   float* cv = cand_v.data_ptr<float>();
   int* ci = cand_i.data_ptr<int>();
